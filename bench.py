@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- Groth16 proofs/sec on the synthetic 2^20-constraint chain QAP (BASELINE.json metric).
 
-  python bench.py --gpus 1 --steps K --warmup W                      (N = 1)
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]   (N = 1)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one groth16::prove of the 2^20-gate chain circuit (m = 2n+2 wires,
@@ -15,9 +15,12 @@ the NTT stage, one all-gather; scaling "strong"; --shard windows | buckets | poi
 `config5` (BASELINE config 5: one proof at a time over N GPUs, the faster of the window shard and its balanced bucket-range form).
 
 Prints ONE JSON line on rank 0 with the contract fields plus `roofline` (dominant kernel, HIP-event
-timed inside the library over the timed region) and, at N = 1, `cpu_baseline` (the CPU oracle's
-faithful restatement of the reference's prove() timed on this host, single thread like the
-reference, on a bounded sample).
+timed inside the library over the timed region).  A plain run sets up, warms up, times the K steps and
+prints the line.  --full adds what takes work of its own: groth16::verify of set 0's proof
+(`config.verified`) and, at N = 1, the PCIe-inclusive leg (`pcie_inclusive`) and `cpu_baseline` (the
+CPU oracle's faithful restatement of the reference's prove() timed on this host, single thread like
+the reference, on a bounded sample).  --dump-outputs DIR writes the last timed step's proof bytes to
+DIR/proof.npy (float64, one element per byte; rank 0) for output-for-output comparisons of builds.
 """
 import argparse
 import json
@@ -312,7 +315,13 @@ def main():
                     help="N > 1: bound (s) of every wait on a peer -- rendezvous, communicator set-up, each collective inside the library, "
                          "each leg; what does not complete in time degrades to independent provers")
     ap.add_argument("--sets", type=int, default=WITNESS_SETS, help="distinct (witness, r, s) the timed region cycles through")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the secondary measurements and checks: groth16::verify of set 0's proof, the PCIe-inclusive leg and "
+                         "the CPU baselines (N = 1); a plain run only sets up, warms up and times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the proof of the last timed step as DIR/proof.npy (float64, one element per "
+                         "byte of the 259-byte proof; rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
     ap.add_argument("--kernel-times", action="store_true",
                     help="event-time every launch group of a proof, not only the bucket accumulations (kernel_ms_per_proof then lists them "
                          "all; costs ~1 %% of the rate)")
@@ -325,8 +334,12 @@ def main():
                     help="one proof at a time (--depth 1), no per-kernel event timing (two extra API calls per launch, which small "
                          "circuits feel), no CPU baseline: ms_per_step is the latency of a lone zk_prove_dev call")
     ap.add_argument("--cpu-baseline", choices=["default", "full"], default="default",
-                    help="full: also the same-algorithm CPU path at 2^20 on ONE thread (minutes)")
+                    help="full (implies --full): also the same-algorithm CPU path at 2^20 on ONE thread (minutes)")
     args = ap.parse_args()
+    if args.cpu_baseline == "full":
+        args.full = True
+    if args.dump_outputs and args.emulate_world:
+        raise SystemExit("--dump-outputs: --emulate-world times partial work and produces no proofs")
     if args.latency:
         args.depth, args.no_cpu_baseline = 1, True
     if args.roots != "unity":
@@ -590,7 +603,7 @@ def main():
     sha = lambda b: __import__("hashlib").sha256(b).hexdigest()[:16]   # noqa: E731
     # groth16::verify (mod.rs:299-320) of set 0's proof: the pairing check shares no code with the prover or with the closed form the
     # tests use, and it is the only reader of sum_gamma / [gamma]_2 of this CRS (untimed; 36 ms on the host)
-    verified = bool(ctx.verify(inst["crs"], sets[0]["weights"][1:1 + inst["l"]], expected[0]))
+    verified = bool(ctx.verify(inst["crs"], sets[0]["weights"][1:1 + inst["l"]], expected[0])) if args.full else None
     for j, pr in run(args.warmup + PRIME, "single"):
         assert pr == expected[j], "pipelined proof differs from the synchronous one"
     torch.cuda.synchronize()
@@ -660,6 +673,8 @@ def main():
             prof_ = ctx.profile()
             ctx.set_option("profile", 0)
         wrong = sum(1 for j, pr in outs if pr != expected[j])
+        if outs:
+            state.setdefault("last_proof", {})[mode] = outs[-1][1]     # what the last timed step gave its caller (--dump-outputs)
         return elapsed, wrong, prof_
 
     def leg_record(name, mode, elapsed, wrong, per_step):
@@ -756,11 +771,15 @@ def main():
     for k_, v_ in legs.items():
         assert v_.get("bytes_equal_to_single_gpu_prove", True), "the %s leg produced different proof bytes" % k_
     proof = expected[0]
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        last = np.frombuffer(state["last_proof"][primary], dtype=np.uint8)
+        np.save(os.path.join(args.dump_outputs, "proof.npy"), last.astype(np.float64))
 
     # beside the resident-witness line: the same steps with every proof's witness handed over in page-locked HOST memory, as the
     # reference's prove(&[T]) does (mod.rs:213-217) -- 67 MB over PCIe per proof at 2^20.  Secondary object, never `value`.
     pcie = None
-    if world == 1 and host_ws is None and args.batch <= 1 and not args.latency:
+    if args.full and world == 1 and host_ws is None and args.batch <= 1 and not args.latency:
         host_ws = []
         for st in sets:
             hw = ctx.host_alloc(st["weights"].shape)
@@ -909,7 +928,8 @@ def main():
                                                 "`window_shard` object of the same line",
                        "setup_steps_before_warmup": PRIME + len(sets), "witness_from": args.witness_from, "witness_sets": len(sets),
                        "proofs_in_flight": depth if args.batch <= 1 else "2 batches of %d" % args.batch, "msm_window_bits": args.window_bits or "auto",
-                       "proof_sha": sha(expected[0]), "proof_shas": [sha(e_) for e_ in expected], "verified": verified,
+                       "proof_sha": sha(expected[0]), "proof_shas": [sha(e_) for e_ in expected],
+                       **({"verified": verified} if verified is not None else {}),
                        "expected_bytes_from": "one synchronous single-GPU zk_prove_dev per set in the untimed set-up; every timed proof is compared with it"},
             "roofline": roofline,
             "kernels": kernels,
@@ -937,7 +957,7 @@ def main():
             **({"host": {"submit_ms_per_proof": round(1e3 * state["submit_s"] / state["submits"], 3),
                          "note": "wall time of zk_prove_submit on the host (everything of a proof is enqueued inside it)"}} if state.get("submits") else {}),
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(zk, ctx, args.seed, inst, args.cpu_baseline == "full")
             out["cpu_baseline"]["cores_on_host"] = os.cpu_count()
         print(json.dumps(out), flush=True)

@@ -97,7 +97,9 @@ def test_one_rank_communicator_through_rccl(tmp_path):
     program's multi-GPU section must still give zk_prove's bytes; then the same from a process that has torch (and its own
     bundled librccl) loaded, as bench.py does."""
     exe = build_shim(tmp_path)
-    env = dict(os.environ, ZK_COMM_FORCE_RCCL="1")
+    # one rank in one process: RCCL's bootstrap talks only to itself, so it listens on loopback -- the address it would otherwise
+    # pick on the host's first external interface may not be reachable from the host itself (filtered), and then the init never returns
+    env = dict(os.environ, ZK_COMM_FORCE_RCCL="1", NCCL_SOCKET_IFNAME="lo")
     res = subprocess.run([exe, os.path.join(ROOT, "tests", "golden", "zk", "simple.zk")] + g2_generator_packed(), capture_output=True, text=True,
                          timeout=600, env=env)
     assert res.returncode == 0 and "ok multi_gpu_world_1" in res.stdout, res.stdout + res.stderr

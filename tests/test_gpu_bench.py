@@ -21,7 +21,7 @@ def last_json_line(out):
 
 
 def test_bench_line_single_gpu():
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "6", "--warmup", "1", "--log-n", "12"],
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "6", "--warmup", "1", "--log-n", "12", "--full"],
                          capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert res.returncode == 0, res.stdout + res.stderr
     d = last_json_line(res.stdout)
@@ -43,6 +43,26 @@ def test_bench_line_single_gpu():
     v = d["roofline"].get("valu")
     if v:       # the sustained issue rates come from the micro-benchmark's committed output
         assert v["peak_measured_source"].startswith("profiles/")
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain run (no --full): the contract fields, exactly --steps timed steps, none of the secondary measurements, and with
+    --dump-outputs the proof of the LAST timed step -- set (steps - 1) mod sets of the cycle -- as float64 bytes."""
+    import hashlib
+    import numpy as np
+    out = tmp_path / "out"
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "1", "--log-n", "12",
+                          "--dump-outputs", str(out)], capture_output=True, text=True, timeout=900, cwd=ROOT)
+    assert res.returncode == 0, res.stdout + res.stderr
+    d = last_json_line(res.stdout)
+    assert KEYS <= set(d) and d["steps"] == 7 and d["value"] > 0 and d["ms_per_step"] > 0 and d["higher_is_better"] is True
+    assert abs(d["value"] * d["ms_per_step"] - 1e3) < 1e-2 * 1e3
+    assert "cpu_baseline" not in d and "pcie_inclusive" not in d and "verified" not in d["config"]
+    p = np.load(str(out / "proof.npy"))
+    assert p.dtype == np.float64 and p.shape == (259,) and np.all((p >= 0) & (p <= 255) & (p == np.round(p)))
+    last = p.astype(np.uint8).tobytes()
+    c = d["config"]
+    assert hashlib.sha256(last).hexdigest()[:16] == c["proof_shas"][(7 - 1) % c["witness_sets"]]
 
 
 def run_two_ranks(extra, env=None, port_base=29600, backend="gloo"):
