@@ -46,8 +46,14 @@ int zk_profile_entry(const zk_ctx* ctx, int i, const char** name, double* total_
  *   ZK_LAZY_SQR        a a 2^-261          (|limbs| < 2^29)
  *   ZK_LAZY_MONT_DIFF  (a b - c d) 2^-261  (all |limbs| < 2^29)
  *   ZK_LAZY_NORM       a after carry propagation; ZK_LAZY_STORE  a itself        (|value| < 8 p)
- *   ZK_LAZY_FR_REDUCE  fr_reduce(a) of the NTT tiles (|value| < 2^9 r); ZK_LAZY_FR_STORE  fr_store_exact(a)   (Fr only) */
-enum { ZK_LAZY_MONT = 0, ZK_LAZY_SQR = 1, ZK_LAZY_MONT_DIFF = 2, ZK_LAZY_NORM = 3, ZK_LAZY_STORE = 4, ZK_LAZY_FR_REDUCE = 5, ZK_LAZY_FR_STORE = 6 };
+ *   ZK_LAZY_FR_REDUCE  fr_reduce(a) of the NTT tiles (|value| < 2^9 r); ZK_LAZY_FR_STORE  fr_store_exact(a)   (Fr only)
+ * The Fq2 multiplier of the G2 accumulation and the G2 tails (Fq only, field 1): one element = two Fq components, each 9 limbs as
+ * above (components with |limbs| < 2^29 and |value| < 8 q).  out holds 2 n residues, c0 then c1 of each element (8 words per
+ * element); raw_out 18 limbs per element, c0's 9 then c1's 9.
+ *   ZK_LAZY_FP2_MUL    (a + b i)(c + d i) 2^-261 = (a c - b d) 2^-261 + (a d + b c) 2^-261 i   (Fp2R::operator*)
+ *   ZK_LAZY_FP2_SQR    (a + b i)^2 2^-261                                                   (Fp2R::sqr; operands a, b) */
+enum { ZK_LAZY_MONT = 0, ZK_LAZY_SQR = 1, ZK_LAZY_MONT_DIFF = 2, ZK_LAZY_NORM = 3, ZK_LAZY_STORE = 4, ZK_LAZY_FR_REDUCE = 5, ZK_LAZY_FR_STORE = 6,
+       ZK_LAZY_FP2_MUL = 7, ZK_LAZY_FP2_SQR = 8 };
 int zk_lazy29_batch(zk_ctx* ctx, int field, int op, const int32_t* a, const int32_t* b, const int32_t* c, const int32_t* d, size_t n,
                     uint64_t* out, int32_t* raw_out);
 

@@ -14,6 +14,8 @@ import pytest
 import zksnark_rs_amd as zk
 from zksnark_rs_amd import SplitMix64, ints_to_limbs, limbs_to_int, R_MODULUS, Q_MODULUS
 
+from test_gpu_edges import uniform_fr
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 pytestmark = pytest.mark.gpu
@@ -121,12 +123,11 @@ def test_ntt_matches_fast_oracle(ctx, orc, log_n, coset):
 
 
 def test_ntt_full_size_properties(ctx):
-    """2^20 (BASELINE size): round trip + linearity + a known transform (delta -> all ones)."""
+    """2^20 (BASELINE size): round trip + linearity + a known transform (delta -> all ones); inputs uniform over all of [0, r)."""
     log_n = 20
     n = 1 << log_n
     rng = np.random.default_rng(1)
-    a = rng.integers(0, 1 << 62, size=(n, 4), dtype=np.uint64)
-    a[:, 3] &= np.uint64((1 << 60) - 1)
+    a = uniform_fr(rng, n)
     fa = ctx.ntt_fr(a)
     assert np.array_equal(ctx.ntt_fr(fa, inverse=True), a)
     b = np.roll(a, 1, axis=0)
@@ -140,11 +141,10 @@ def test_ntt_full_size_properties(ctx):
 @pytest.mark.parametrize("log_n", [23, 24])
 def test_ntt_three_passes(ctx, orc, log_n):
     """sizes above 2^22 take one more column pass (ntt.hip): == the oracle's NTT at 2^23 (plain and coset), round trips, a
-    delta -> all ones, a shifted delta -> the powers of w at sampled positions"""
+    delta -> all ones, a shifted delta -> the powers of w at sampled positions; inputs uniform over all of [0, r)"""
     n = 1 << log_n
     rng = np.random.default_rng(log_n)
-    a = rng.integers(0, 1 << 62, size=(n, 4), dtype=np.uint64)
-    a[:, 3] &= np.uint64((1 << 60) - 1)
+    a = uniform_fr(rng, n)
     fa = ctx.ntt_fr(a)
     assert np.array_equal(ctx.ntt_fr(fa, inverse=True), a)
     if log_n == 23:

@@ -10,7 +10,7 @@ import zksnark_rs_amd as zk
 from zksnark_rs_amd import _lib
 
 P = {0: zk.R_MODULUS, 1: zk.Q_MODULUS}
-MONT, SQR, MONT_DIFF, NORM, STORE, FR_REDUCE, FR_STORE = range(7)
+MONT, SQR, MONT_DIFF, NORM, STORE, FR_REDUCE, FR_STORE, FP2_MUL, FP2_SQR = range(9)
 RINV = {f: pow(1 << 261, -1, p) for f, p in P.items()}
 M29 = (1 << 29) - 1
 
@@ -137,6 +137,67 @@ def test_ntt_tile_reductions(ctx):
     assert run(ctx, 0, FR_STORE, pats) == [value(q) % r for q in pats]
 
 
+def run_fp2(ctx, op, *ops):
+    """the Fq2 ops (field 1): element i = ops[0][i] + ops[1][i] i, times ops[2][i] + ops[3][i] i for FP2_MUL; returns the
+    canonical (c0, c1) pairs and the 18 raw limbs per element"""
+    arrs = [np.ascontiguousarray(np.array(o, dtype=np.int64).astype(np.int32).reshape(-1, 9)) for o in ops]
+    n = arrs[0].shape[0]
+    ptrs = [a.ctypes.data_as(_lib.i32p) for a in arrs] + [None] * (4 - len(arrs))
+    out = np.zeros((n, 2, 4), np.uint64)
+    raw = np.zeros((n, 18), np.int32)
+    ctx._check(ctx.lib.zk_lazy29_batch(ctx.ptr, 1, op, *ptrs, n, out.ctypes.data_as(_lib.u64p), raw.ctypes.data_as(_lib.i32p)))
+    return [(zk.limbs_to_int(o[0]), zk.limbs_to_int(o[1])) for o in out], raw
+
+
+def fp2_operands(rng):
+    """Fq2 operands at Fp2R's contract (lazy29.cuh: components with |limb| < 2^29, normal forms or differences of two; |value| < 8 q)"""
+    q = P[1]
+    X = patterns(rng, M29, q, 8)
+    neg = lambda x: [-v for v in x]                      # noqa: E731
+    ext = X[:4]                                          # every limb at +(2^29 - 1) / -(2^29 - 1) / alternating, top limb at the bound
+    signed = [x for e in ext for x in (e, neg(e))]
+    elems = [(X[i], X[(7 * i + 1) % len(X)]) for i in range(len(X))]
+    return X, signed, elems
+
+
+def _fp2_contract(raw, bound):
+    """normal form (limbs 0..7 of each component in [0, 2^29)), each component within (-lim, lim + q) for lim = its |product| / 2^261"""
+    q = P[1]
+    for k, (v, lim) in enumerate(zip((value(raw[:9]), value(raw[9:])), bound)):
+        assert all(0 <= int(x) <= M29 for x in raw[9 * k:9 * k + 8])
+        assert -(lim // (1 << 261)) - 1 <= v <= lim // (1 << 261) + 1 + q
+
+
+@pytest.mark.gpu
+def test_fp2_mul_and_sqr_at_the_limb_bounds(ctx):
+    """Fp2R::operator* (mont_asm_fp2 on the device: the multiplier of the G2 accumulation and of every G2 tail kernel) and Fp2R::sqr at
+    the extremes of their operand contract, against Python big ints: (a0 b0 - a1 b1) 2^-261 and (a0 b1 + a1 b0) 2^-261 mod q.  Every
+    sign combination of the extreme limb vectors in the four components is included, so each output column sees its 18 products with
+    one sign (the c0 column when sign(a0 b0) = -sign(a1 b1), the c1 column when sign(a0 b1) = sign(a1 b0); both at once is impossible)."""
+    q, rinv = P[1], RINV[1]
+    rng = np.random.default_rng(41)
+    X, signed, elems = fp2_operands(rng)
+    quads = [(a0, a1, b0, b1) for a0 in signed for a1 in signed[:4] for b0 in signed[:4] for b1 in signed]
+    quads += [(a[0], a[1], b[0], b[1]) for a in elems for b in elems[:16]]
+    for k in (-2, 1, 7):                                  # k q +- 1 in every position
+        for d in (-1, 1):
+            e = normal_form(k * q + d)
+            quads += [(e, X[0], X[1], e), (X[0], e, e, X[1]), (e, e, e, e)]
+    got, raw = run_fp2(ctx, FP2_MUL, *[[t[i] for t in quads] for i in range(4)])
+    assert len(got) == len(quads)
+    for (a0, a1, b0, b1), g, rw in zip(quads, got, raw):
+        va0, va1, vb0, vb1 = value(a0), value(a1), value(b0), value(b1)
+        assert g == ((va0 * vb0 - va1 * vb1) * rinv % q, (va0 * vb1 + va1 * vb0) * rinv % q)
+        _fp2_contract(rw, (abs(va0 * vb0) + abs(va1 * vb1), abs(va0 * vb1) + abs(va1 * vb0)))
+        assert abs(value(rw[:9])) < 2 * q and abs(value(rw[9:])) < 2 * q          # lazy29.cuh: |value| < 2 (8q)^2 / 2^261 + q < 2q
+    pairs = [(a0, a1) for a0 in signed for a1 in signed] + elems
+    got, raw = run_fp2(ctx, FP2_SQR, [p[0] for p in pairs], [p[1] for p in pairs])
+    for (a0, a1), g, rw in zip(pairs, got, raw):
+        va0, va1 = value(a0), value(a1)
+        assert g == ((va0 * va0 - va1 * va1) * rinv % q, 2 * va0 * va1 * rinv % q)
+        _fp2_contract(rw, (abs((va0 + va1) * (va0 - va1)), abs(2 * va0 * va1)))
+
+
 @pytest.mark.gpu
 def test_lazy29_argument_errors(ctx):
     a = np.zeros((1, 9), np.int32)
@@ -146,6 +207,16 @@ def test_lazy29_argument_errors(ctx):
     assert ctx.lib.zk_lazy29_batch(ctx.ptr, 1, FR_REDUCE, ap, None, None, None, 1, op, None) == -1   # Fr-only op
     assert ctx.lib.zk_lazy29_batch(ctx.ptr, 0, MONT, ap, None, None, None, 1, op, None) == -1        # missing operand
     assert ctx.lib.zk_lazy29_batch(ctx.ptr, 0, 9, ap, None, None, None, 1, op, None) == -1
+    assert ctx.lib.zk_lazy29_batch(ctx.ptr, 1, 9, ap, ap, ap, ap, 1, op, None) == -1
+    out2 = np.zeros((1, 8), np.uint64)
+    op2 = out2.ctypes.data_as(_lib.u64p)
+    for fop in (FP2_MUL, FP2_SQR):
+        assert ctx.lib.zk_lazy29_batch(ctx.ptr, 0, fop, ap, ap, ap, ap, 1, op2, None) == -1      # Fq2 exists over Fq only
+    assert ctx.lib.zk_lazy29_batch(ctx.ptr, 1, FP2_MUL, ap, ap, ap, None, 1, op2, None) == -1     # missing operand
+    assert ctx.lib.zk_lazy29_batch(ctx.ptr, 1, FP2_MUL, ap, ap, None, ap, 1, op2, None) == -1
+    assert ctx.lib.zk_lazy29_batch(ctx.ptr, 1, FP2_SQR, ap, None, None, None, 1, op2, None) == -1
+    assert ctx.lib.zk_lazy29_batch(ctx.ptr, 1, FP2_MUL, ap, ap, ap, ap, 1, op2, None) == 0       # and the valid call works
+    assert ctx.lib.zk_lazy29_batch(ctx.ptr, 1, FP2_SQR, ap, ap, None, None, 1, op2, None) == 0
 
 
 def test_three_inversions_agree_on_the_host(tmp_path):

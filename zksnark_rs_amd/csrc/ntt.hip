@@ -534,16 +534,33 @@ __global__ void k_lazy29_fr(int op, const int32_t* __restrict__ a, size_t n, Fr*
     if (raw)
         for (int k = 0; k < 9; ++k) raw[i * 9 + k] = r.v[k];
 }
+// the Fq2 product (Fp2R::operator*: mont_asm_fp2 in the device build) and square; element i = (a_i + b_i i), second factor (c_i + d_i i)
+__global__ void k_lazy29_fp2(int op, const int32_t* __restrict__ a, const int32_t* __restrict__ b, const int32_t* __restrict__ c, const int32_t* __restrict__ d,
+                             size_t n, Fq2* __restrict__ out, int32_t* __restrict__ raw) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    typedef Fp2R<FqParams> L2;
+    const L2 x{lazy_get<FqParams>(a, i), lazy_get<FqParams>(b, i)};
+    const L2 r = op == ZK_LAZY_FP2_MUL ? x * L2{lazy_get<FqParams>(c, i), lazy_get<FqParams>(d, i)} : x.sqr();
+    out[i] = r.store_exact();
+    if (raw)
+        for (int k = 0; k < 9; ++k) {
+            raw[i * 18 + k] = r.c0.v[k];
+            raw[i * 18 + 9 + k] = r.c1.v[k];
+        }
+}
 void lazy29_batch(zk_ctx* ctx, int field, int op, const int32_t* a, const int32_t* b, const int32_t* c, const int32_t* d, size_t n, uint64_t* out, int32_t* raw_out) {
     ZK_REQUIRE(field == 0 || field == 1, ZK_ERR_ARG, "zk_lazy29_batch: field must be 0 (Fr) or 1 (Fq)");
-    ZK_REQUIRE(op >= ZK_LAZY_MONT && op <= ZK_LAZY_FR_STORE, ZK_ERR_ARG, "zk_lazy29_batch: unknown op");
-    ZK_REQUIRE(op < ZK_LAZY_FR_REDUCE || field == 0, ZK_ERR_ARG, "zk_lazy29_batch: fr_reduce / fr_store_exact exist for Fr only");
-    const int operands = op == ZK_LAZY_MONT ? 2 : op == ZK_LAZY_MONT_DIFF ? 4 : 1;
+    ZK_REQUIRE(op >= ZK_LAZY_MONT && op <= ZK_LAZY_FP2_SQR, ZK_ERR_ARG, "zk_lazy29_batch: unknown op");
+    ZK_REQUIRE(op < ZK_LAZY_FR_REDUCE || op > ZK_LAZY_FR_STORE || field == 0, ZK_ERR_ARG, "zk_lazy29_batch: fr_reduce / fr_store_exact exist for Fr only");
+    const bool fp2 = op >= ZK_LAZY_FP2_MUL;
+    ZK_REQUIRE(!fp2 || field == 1, ZK_ERR_ARG, "zk_lazy29_batch: the Fq2 product and square exist for Fq only");
+    const int operands = op == ZK_LAZY_MONT || op == ZK_LAZY_FP2_SQR ? 2 : op == ZK_LAZY_MONT_DIFF || op == ZK_LAZY_FP2_MUL ? 4 : 1;
     ZK_REQUIRE(out && (n == 0 || (a && (operands < 2 || b) && (operands < 4 || (c && d)))), ZK_ERR_ARG, "zk_lazy29_batch: null pointer");
     if (!n) return;
-    const size_t limbs = n * 9;
-    DevBuf<int32_t> da(limbs), db(operands >= 2 ? limbs : 0), dc(operands >= 4 ? limbs : 0), dd(operands >= 4 ? limbs : 0), draw(raw_out ? limbs : 0);
-    DevBuf<Fr> dout(n);
+    const size_t limbs = n * 9, elems = fp2 ? 2 * n : n;
+    DevBuf<int32_t> da(limbs), db(operands >= 2 ? limbs : 0), dc(operands >= 4 ? limbs : 0), dd(operands >= 4 ? limbs : 0), draw(raw_out ? elems * 9 : 0);
+    DevBuf<Fr> dout(elems);
     hipStream_t st = ctx->stream;
     ZK_HIP(hipMemcpyAsync(da.p, a, limbs * 4, hipMemcpyHostToDevice, st));
     if (operands >= 2) ZK_HIP(hipMemcpyAsync(db.p, b, limbs * 4, hipMemcpyHostToDevice, st));
@@ -552,12 +569,13 @@ void lazy29_batch(zk_ctx* ctx, int field, int op, const int32_t* a, const int32_
         ZK_HIP(hipMemcpyAsync(dd.p, d, limbs * 4, hipMemcpyHostToDevice, st));
     }
     const dim3 grid(ceil_div(n, 256)), block(256);
-    if (op >= ZK_LAZY_FR_REDUCE) hipLaunchKernelGGL(k_lazy29_fr, grid, block, 0, st, op, da.p, n, dout.p, draw.p);
+    if (fp2) hipLaunchKernelGGL(k_lazy29_fp2, grid, block, 0, st, op, da.p, db.p, dc.p, dd.p, n, reinterpret_cast<Fq2*>(dout.p), draw.p);
+    else if (op >= ZK_LAZY_FR_REDUCE) hipLaunchKernelGGL(k_lazy29_fr, grid, block, 0, st, op, da.p, n, dout.p, draw.p);
     else if (field == 0) hipLaunchKernelGGL(k_lazy29<FrParams>, grid, block, 0, st, op, da.p, db.p, dc.p, dd.p, n, dout.p, draw.p);
     else hipLaunchKernelGGL(k_lazy29<FqParams>, grid, block, 0, st, op, da.p, db.p, dc.p, dd.p, n, reinterpret_cast<Fq*>(dout.p), draw.p);
     ZK_HIP(hipGetLastError());
-    ZK_HIP(hipMemcpyAsync(out, dout.p, n * sizeof(Fr), hipMemcpyDeviceToHost, st));
-    if (raw_out) ZK_HIP(hipMemcpyAsync(raw_out, draw.p, limbs * 4, hipMemcpyDeviceToHost, st));
+    ZK_HIP(hipMemcpyAsync(out, dout.p, elems * sizeof(Fr), hipMemcpyDeviceToHost, st));
+    if (raw_out) ZK_HIP(hipMemcpyAsync(raw_out, draw.p, elems * 9 * 4, hipMemcpyDeviceToHost, st));
     ZK_HIP(hipStreamSynchronize(st));
 }
 
