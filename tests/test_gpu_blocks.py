@@ -316,7 +316,10 @@ def test_msm_accumulation_meets_its_own_sum(ctx, orc, c):
       {A, B, D,   A+B+D }   the same point at position 4 when the sum comes last (a quarter of the buckets): doubling
       {A, B, -(A+B), D}     P + (-P) at position 3 (the even body) when D comes last; then D starts the accumulator again
       {A, B,   A+B,  D}     doubling at position 3 in a twelfth of the buckets
-      {A, inf, B, D}        a table entry at infinity inside the run (the lane leaves the fast loop without consuming it)
+      {A, inf, B, D}        a table entry at infinity: at position 1 or 2 the generic steps skip it; at 3 the lane leaves the fast loop
+                            from its first even half (canonical state), at 4 -- the run's last entry -- from its first odd half (a
+                            quarter of these buckets each).  Later trips, consecutive infinities, infinity behind a same-x event
+                            and runs of infinity: tests/test_gpu_circuit_shapes.py
     Scalars are single digits of window 0, so bucket d holds exactly the points given scalar d (and G2 takes the same route through its
     own loop).  Against the oracle's folded double-and-add."""
     rng = SplitMix64(6100 + c)
