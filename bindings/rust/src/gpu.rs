@@ -66,6 +66,8 @@ extern "C" {
     fn zk_prove(ctx: *mut ZkCtx, crs: *const ZkCrs, qap: *const ZkQap, weights: *const u64, m: usize,
                 r: *const u64, s: *const u64, proof_out: *mut u8) -> c_int;
     fn zk_verify(ctx: *mut ZkCtx, crs: *const ZkCrs, inputs: *const u64, n_inputs: usize, proof: *const u8, ok: *mut c_int) -> c_int;
+    fn zk_verify_batch(ctx: *mut ZkCtx, crs: *const ZkCrs, inputs: *const u64, n_inputs: usize, proofs: *const u8, n_proofs: usize,
+                       ok: *mut c_int) -> c_int;
     // a stream of proofs: witnesses in page-locked host memory, two tickets in flight
     fn zk_host_alloc(bytes: usize, out: *mut *mut c_void) -> c_int;
     fn zk_host_free(p: *mut c_void);
@@ -532,6 +534,17 @@ impl GpuProver {
         let (x, bytes, mut ok) = (frs(inputs), proof_to_bytes(proof), 0 as c_int);
         unsafe { check(self.ctx.0, zk_verify(self.ctx.0, self.crs, x.as_ptr(), inputs.len(), bytes.as_ptr(), &mut ok)); }
         ok == 1
+    }
+    /// verify for many proofs on the GPU (zk_verify_batch): entry j == verify(&inputs[j], &proofs[j]); every row has the same length
+    pub fn verify_batch(&self, inputs: &[Vec<FrLocal>], proofs: &[Proof<G1Local, G2Local>]) -> Vec<bool> {
+        assert!(inputs.len() == proofs.len(), "one input row per proof");
+        let k = inputs.first().map_or(0, |r| r.len());
+        assert!(inputs.iter().all(|r| r.len() == k), "every proof needs the same number of inputs");
+        let x: Vec<u64> = inputs.iter().flat_map(|r| frs(r)).collect();
+        let bytes: Vec<u8> = proofs.iter().flat_map(|p| proof_to_bytes(p).to_vec()).collect();
+        let mut ok = vec![0 as c_int; proofs.len()];
+        unsafe { check(self.ctx.0, zk_verify_batch(self.ctx.0, self.crs, x.as_ptr(), k, bytes.as_ptr(), proofs.len(), ok.as_mut_ptr())); }
+        ok.into_iter().map(|v| v == 1).collect()
     }
     /// Many proofs over one circuit: the 32 m-byte transfer of witness k+1 overlaps the inner products of proof k
     /// (zk_prove_submit_host / zk_prove_wait with two tickets in flight and page-locked staging buffers).

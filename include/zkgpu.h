@@ -438,6 +438,18 @@ int zk_mgpu_create_custom(zk_comm* comm, const zk_mgpu_backend* backend, zk_mgpu
  * < q on the curve, never (0, 0)) and B must lie in the order-r subgroup G2 of the twist ([r]B = infinity is checked:
  * the twist's cofactor has small factors and the pairing is bilinear only on G2). */
 int zk_verify(zk_ctx* ctx, const zk_crs* crs, const uint64_t* inputs, size_t n_inputs, const uint8_t proof[ZK_PROOF_BYTES], int* ok);
+/* Batch verify on the GPU: ok[j] = what zk_verify(ctx, crs, inputs + 4 n_inputs j, n_inputs, proofs + ZK_PROOF_BYTES j, &ok)
+ * writes, for every j < n_proofs.  proofs: n_proofs x ZK_PROOF_BYTES bytes; inputs: n_proofs rows of n_inputs Fr values
+ * (4 words each), the same count for every proof; as in zk_verify only the first min(l, n_inputs) of a row are read.
+ * n_proofs == 0: ZK_OK, nothing written.  Null ctx / crs / proofs / ok, or null inputs with n_inputs > 0: ZK_ERR_ARG.  An input
+ * >= r among those read: ZK_ERR_RANGE and every ok[j] = 0, decided on the host before anything is launched.  A CRS point off
+ * its curve or outside G2: ZK_ERR_ARG.  Any n_proofs: the proofs go through the device ZK_VERIFY_BATCH_CHUNK at a time
+ * (device memory ~1.2 KB + 32 min(l, n_inputs) bytes per proof of a chunk); the verdicts do not depend on the chunking.
+ * Synchronous: returns when the verdicts are in host memory.  It runs on a stream of its own and waits only on that stream
+ * (no device-wide synchronisation): a zk_prove_submit ticket outstanding on the same context is neither waited for nor
+ * disturbed. */
+#define ZK_VERIFY_BATCH_CHUNK 65536
+int zk_verify_batch(zk_ctx* ctx, const zk_crs* crs, const uint64_t* inputs, size_t n_inputs, const uint8_t* proofs, size_t n_proofs, int* ok);
 /* EllipticEncryptable::pairing (fr.rs:120-122): the optimal ate pairing e(P, Q) as 12 Fq coefficients
  * (48 words) in the order c0.a0.c0, c0.a0.c1, c0.a1.c0, ..., c1.a2.c1 of the tower
  * Fq12 = Fq6[w]/(w^2 - v), Fq6 = Fq2[v]/(v^3 - (9+i)).  Host only; needs no context.  ZK_ERR_RANGE when a coordinate

@@ -289,5 +289,23 @@ inline bool verify(const Context& c, const Sigma& sigma, const std::vector<FrLoc
     return ok != 0;
 }
 
+// verify for many proofs over one CRS on the GPU (zk_verify_batch): entry j == verify(c, sigma, inputs[j], proofs[j]); every
+// inputs[j] has the same length
+inline std::vector<bool> verify_batch(const Context& c, const Sigma& sigma, const std::vector<std::vector<FrLocal>>& inputs,
+                                      const std::vector<Proof>& proofs) {
+    if (inputs.size() != proofs.size()) throw Error(ZK_ERR_ARG, "groth16::verify_batch: one input row per proof");
+    const size_t n = proofs.size(), k = n ? inputs[0].size() : 0;
+    std::vector<uint64_t> x(n * k * 4);
+    std::vector<uint8_t> bytes(n * ZK_PROOF_BYTES);
+    for (size_t j = 0; j < n; ++j) {
+        if (inputs[j].size() != k) throw Error(ZK_ERR_ARG, "groth16::verify_batch: every proof needs the same number of inputs");
+        for (size_t i = 0; i < k; ++i) std::copy(inputs[j][i].w.begin(), inputs[j][i].w.end(), x.begin() + (j * k + i) * 4);
+        std::copy(proofs[j].bytes.begin(), proofs[j].bytes.end(), bytes.begin() + j * ZK_PROOF_BYTES);
+    }
+    std::vector<int> ok(n, 0);
+    c.check(zk_verify_batch(c.get(), sigma.get(), k ? x.data() : nullptr, k, bytes.data(), n, ok.data()), "groth16::verify_batch");
+    return std::vector<bool>(ok.begin(), ok.end());
+}
+
 }  // namespace groth16
 }  // namespace zksnark

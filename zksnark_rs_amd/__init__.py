@@ -513,6 +513,30 @@ class Context:
         self._check(self.lib.zk_verify(self.ptr, crs.ptr, a.ctypes.data_as(_lib.u64p), a.shape[0], pb.ctypes.data_as(_lib.u8p), C.byref(ok)))
         return bool(ok.value)
 
+    def verify_batch(self, crs, inputs, proofs):
+        """zk_verify_batch: verify on the GPU for every proof j -> (N,) bool array, entry j == verify(crs, inputs[j], proofs[j]).
+        inputs: (N, k) ints or (N, k, 4) limbs, the same k for every proof; proofs: a list of 259-byte strings or an (N, 259)
+        uint8 array."""
+        if isinstance(proofs, np.ndarray):
+            pb = np.ascontiguousarray(proofs, dtype=np.uint8).reshape(-1, PROOF_BYTES)
+        else:
+            pb = np.frombuffer(b"".join(bytes(p) for p in proofs), dtype=np.uint8).reshape(-1, PROOF_BYTES).copy()
+        n = pb.shape[0]
+        if isinstance(inputs, np.ndarray) and inputs.ndim == 3:
+            a = np.ascontiguousarray(inputs, dtype=np.uint64)
+        else:
+            rows = [[int(x) for x in r] for r in inputs]
+            k = len(rows[0]) if rows else 0
+            if any(len(r) != k for r in rows):
+                raise ValueError("verify_batch: every proof needs the same number of inputs")
+            a = ints_to_limbs([x for r in rows for x in r]).reshape(len(rows), k, 4)
+        if a.shape[0] != n or a.shape[2:] != (4,):
+            raise ValueError("verify_batch: inputs must hold one row per proof")
+        ok = np.zeros(n, dtype=np.int32)
+        self._check(self.lib.zk_verify_batch(self.ptr, crs.ptr, a.ctypes.data_as(_lib.u64p) if a.size else None, a.shape[1],
+                                             pb.ctypes.data_as(_lib.u8p), n, ok.ctypes.data_as(C.POINTER(C.c_int))))
+        return ok.astype(bool)
+
     # ---- profiling ----
     def profile_reset(self):
         self._check(self.lib.zk_profile_reset(self.ptr))

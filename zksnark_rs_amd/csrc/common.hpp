@@ -99,6 +99,7 @@ struct PendingEvent {
 struct NttTables;  // ntt.hip
 struct MsmWorkspace;  // kernels.hpp
 struct ProveState;    // prove.hip
+struct VerifyBatchState;   // verify_batch.hip
 
 }  // namespace zk
 
@@ -109,6 +110,7 @@ struct zk_ctx {
     hipStream_t finish = nullptr;  // join + assembly + copy-out of a proof
     hipStream_t main_alt = nullptr;  // second main stream: odd-numbered proof slots run their SpMV / NTT stage here
     std::shared_ptr<zk::ProveState> prove_state;
+    std::shared_ptr<zk::VerifyBatchState> verify_batch;   // zk_verify_batch: its stream and buffers
     hipEvent_t submit_wait_evt = nullptr;   // consumed by the next prove_submit / prove_msm_submit: its first kernels wait for this event (comm.hip)
     int cur_slot = -1;
     std::string last_error;

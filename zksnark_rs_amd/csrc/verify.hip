@@ -10,64 +10,9 @@
 // with (q^12 - 1)/r.  The four pairings of the check share one final exponentiation:
 //   e(alpha,beta) e(S,gamma) e(C,delta) == e(A,B)  <=>  FE(ml(alpha,beta) ml(S,gamma) ml(C,delta) ml(-A,B)) == 1.
 #include "pipeline.hpp"
-#include "pairing_consts.hpp"
+#include "pairing.cuh"
 
 namespace zk {
-
-static Fq fq_small(uint32_t v) { return Fq::from_u32(v); }
-static Fq2 fq2_mul_xi(const Fq2& a) {   // (9 + i) * a
-    Fq n0 = a.c0.dbl().dbl().dbl() + a.c0, n1 = a.c1.dbl().dbl().dbl() + a.c1;
-    return Fq2{n0 - a.c1, n1 + a.c0};
-}
-static Fq2 fq2_conj(const Fq2& a) { return Fq2{a.c0, -a.c1}; }
-static Fq2 fq2_from_words(const uint32_t* w) {
-    Fq2 x;
-    for (int i = 0; i < 8; ++i) { x.c0.l[i] = w[i]; x.c1.l[i] = w[8 + i]; }
-    return Fq2::from_canonical(x);
-}
-
-struct Fq6 {
-    Fq2 a0, a1, a2;
-    static Fq6 zero() { return Fq6{Fq2::zero(), Fq2::zero(), Fq2::zero()}; }
-    static Fq6 one() { return Fq6{Fq2::one(), Fq2::zero(), Fq2::zero()}; }
-    Fq6 operator+(const Fq6& o) const { return Fq6{a0 + o.a0, a1 + o.a1, a2 + o.a2}; }
-    Fq6 operator-(const Fq6& o) const { return Fq6{a0 - o.a0, a1 - o.a1, a2 - o.a2}; }
-    Fq6 operator-() const { return Fq6{-a0, -a1, -a2}; }
-    Fq6 operator*(const Fq6& o) const {
-        Fq2 c0 = a0 * o.a0 + fq2_mul_xi(a1 * o.a2 + a2 * o.a1);
-        Fq2 c1 = a0 * o.a1 + a1 * o.a0 + fq2_mul_xi(a2 * o.a2);
-        Fq2 c2 = a0 * o.a2 + a1 * o.a1 + a2 * o.a0;
-        return Fq6{c0, c1, c2};
-    }
-    Fq6 mul_v() const { return Fq6{fq2_mul_xi(a2), a0, a1}; }
-    Fq6 inv() const {
-        Fq2 t0 = a0.sqr() - fq2_mul_xi(a1 * a2);
-        Fq2 t1 = fq2_mul_xi(a2.sqr()) - a0 * a1;
-        Fq2 t2 = a1.sqr() - a0 * a2;
-        Fq2 d = (a0 * t0 + fq2_mul_xi(a2 * t1 + a1 * t2)).inv();
-        return Fq6{t0 * d, t1 * d, t2 * d};
-    }
-    bool operator==(const Fq6& o) const { return a0 == o.a0 && a1 == o.a1 && a2 == o.a2; }
-};
-struct Fq12 {
-    Fq6 c0, c1;
-    static Fq12 one() { return Fq12{Fq6::one(), Fq6::zero()}; }
-    Fq12 operator*(const Fq12& o) const {
-        Fq6 t0 = c0 * o.c0, t1 = c1 * o.c1;
-        return Fq12{t0 + t1.mul_v(), c0 * o.c1 + c1 * o.c0};
-    }
-    Fq12 sqr() const { return *this * *this; }
-    bool operator==(const Fq12& o) const { return c0 == o.c0 && c1 == o.c1; }
-    Fq12 pow_words(const uint32_t* e, int nwords) const {
-        Fq12 acc = one();
-        bool started = false;
-        for (int i = nwords * 32 - 1; i >= 0; --i) {
-            if (started) acc = acc.sqr();
-            if ((e[i >> 5] >> (i & 31)) & 1) { acc = acc * *this; started = true; }
-        }
-        return acc;
-    }
-};
 
 // line through T and Q2 on the twist (tangent when `dbl`), evaluated at P; T <- T + Q2
 static Fq12 line_and_add(G2A& T, const G2A& Q2, bool dbl, const G1A& P) {
@@ -108,62 +53,6 @@ static Fq12 miller_loop(const G1A& P, const G2A& Q) {
     return f;
 }
 static Fq12 final_exponentiation(const Fq12& f) { return f.pow_words(FINAL_EXP, FINAL_EXP_WORDS); }
-
-static Fq fq_from_u64x4(const uint64_t* w) {
-    Fq x;
-    for (int i = 0; i < 4; ++i) { x.l[2 * i] = (uint32_t)w[i]; x.l[2 * i + 1] = (uint32_t)(w[i] >> 32); }
-    return x;
-}
-static bool rd_g1(const uint64_t* w, G1A& out) {
-    Fq x = fq_from_u64x4(w), y = fq_from_u64x4(w + 4);
-    if (!x.raw_in_range() || !y.raw_in_range()) return false;
-    out = G1A{Fq::from_canonical(x), Fq::from_canonical(y)};
-    if (out.is_inf()) return true;
-    return out.y.sqr() == out.x.sqr() * out.x + fq_small(3);
-}
-static bool rd_g2(const uint64_t* w, G2A& out) {
-    Fq2 x{fq_from_u64x4(w), fq_from_u64x4(w + 4)}, y{fq_from_u64x4(w + 8), fq_from_u64x4(w + 12)};
-    if (!x.raw_in_range() || !y.raw_in_range()) return false;
-    out = G2A{Fq2::from_canonical(x), Fq2::from_canonical(y)};
-    if (out.is_inf()) return true;
-    Fq2 b2 = Fq2{fq_small(3), Fq::zero()} * Fq2{fq_small(9), fq_small(1)}.inv();   // 3 / xi
-    if (!(out.y.sqr() == out.x.sqr() * out.x + b2)) return false;
-    // r-torsion: the twist E'(Fq2) has order r * (2q - r) and the cofactor has small factors; the ate Miller loop is
-    // bilinear only on the order-r subgroup G2, so a twist point outside it is rejected ([r]Q must be infinity).
-    // G1 needs no such test: E(Fq) has prime order r.
-    return jac_mul_words(G2J::from_affine(out), FrParams::P).is_inf();
-}
-static void be_to_words(const uint8_t* be, uint64_t* w) {
-    for (int i = 0; i < 4; ++i) {
-        uint64_t v = 0;
-        for (int b = 0; b < 8; ++b) v = (v << 8) | be[(3 - i) * 8 + b];
-        w[i] = v;
-    }
-}
-// decode the canonical 65 / 129 byte blocks of a proof
-// The encoding is canonical, so that a proof has exactly one byte string: infinity is tag 0x00 followed by zeros ONLY,
-// a finite point is tag 0x04 with coordinates < q that satisfy the curve equation ((0, 0), the in-memory
-// image of infinity, is not on either curve and is rejected under tag 0x04).
-static bool all_zero(const uint8_t* p, size_t n) {
-    uint8_t acc = 0;
-    for (size_t i = 0; i < n; ++i) acc |= p[i];
-    return acc == 0;
-}
-static bool dec_g1(const uint8_t* p, G1A& out) {
-    if (p[0] == 0) { out = G1A::infinity(); return all_zero(p + 1, 64); }
-    if (p[0] != 4) return false;
-    uint64_t w[8];
-    be_to_words(p + 1, w); be_to_words(p + 33, w + 4);
-    return rd_g1(w, out) && !out.is_inf();
-}
-static bool dec_g2(const uint8_t* p, G2A& out) {
-    if (p[0] == 0) { out = G2A::infinity(); return all_zero(p + 1, 128); }
-    if (p[0] != 4) return false;
-    uint64_t w[16];
-    be_to_words(p + 1, w + 4); be_to_words(p + 33, w);          // x.c1 | x.c0
-    be_to_words(p + 65, w + 12); be_to_words(p + 97, w + 8);    // y.c1 | y.c0
-    return rd_g2(w, out) && !out.is_inf();
-}
 
 static void fq12_to_words(const Fq12& f, uint64_t* out) {
     const Fq2* parts[6] = {&f.c0.a0, &f.c0.a1, &f.c0.a2, &f.c1.a0, &f.c1.a1, &f.c1.a2};

@@ -1,0 +1,220 @@
+// verify_batch.hip -- zk_verify_batch: zk_verify for many proofs over one CRS, one lane per proof on the GPU.
+//
+// Per proof j (four kernels, per-proof state in HBM between them):
+//   k_vb_decode   the 259 bytes through the decoder zk_verify uses (pairing.cuh dec_g1 / dec_g2, [r]B == infinity included)
+//   k_vb_inputs   S_j = sum_gamma_0 + sum_{i=1..k} x_ji sum_gamma_i, k = min(l, n_inputs): one shared doubling per bit, a mixed
+//                 addition per set bit (complete formulas, ec.cuh), then affine
+//   k_vb_miller   f_j = ml(S_j, gamma) ml(C_j, delta) ml(-A_j, B_j) with one shared squaring per step, gamma's and delta's lines
+//                 precomputed once per call (fixed argument), B's computed on the fly; times c = ml(alpha, beta), also once per call
+//   k_vb_final    ok_j = decoded_j && final_exp_exact(f_j) == 1
+// The host checks the inputs' range and the CRS points exactly as zk_verify does, computes c and the fixed lines, uploads bytes
+// and inputs and reads the verdicts back.  Everything runs on the call's own stream.
+#define ZK_MUL_OUTLINE 1
+#include "pipeline.hpp"
+#include "pairing.cuh"
+
+namespace zk {
+
+static constexpr int VB_BLOCK = 64;
+
+__global__ void __launch_bounds__(VB_BLOCK) k_vb_decode(const uint8_t* proofs, size_t n, G1A* A, G2A* B, G1A* C, int* decoded) {
+    const size_t j = (size_t)blockIdx.x * VB_BLOCK + threadIdx.x;
+    if (j >= n) return;
+    const uint8_t* p = proofs + j * ZK_PROOF_BYTES;
+    G1A a = G1A::infinity(), c = G1A::infinity();
+    G2A b = G2A::infinity();
+    const bool ok = dec_g1(p, a) && dec_g2(p + 65, b) && dec_g1(p + 194, c);
+    A[j] = a;
+    B[j] = b;
+    C[j] = c;
+    decoded[j] = ok ? 1 : 0;
+}
+
+// x: n rows of k canonical inputs (4 words each), all < r (checked on the host); sg: the k + 1 bases, Montgomery
+__global__ void __launch_bounds__(VB_BLOCK) k_vb_inputs(const uint64_t* x, size_t k, const G1A* sg, size_t n, G1A* S) {
+    const size_t j = (size_t)blockIdx.x * VB_BLOCK + threadIdx.x;
+    if (j >= n) return;
+    const uint64_t* xj = x + j * k * 4;
+    G1J acc = G1J::infinity();
+    if (k) {
+        for (int b = 253; b >= 0; --b) {   // inputs < r < 2^254
+            acc = jac_dbl_ni(acc);
+            for (size_t i = 0; i < k; ++i)
+                if ((xj[4 * i + (b >> 6)] >> (b & 63)) & 1) acc = jac_madd_ni(acc, sg[i + 1]);
+        }
+    }
+    S[j] = jac_to_affine(jac_madd_ni(acc, sg[0]));
+}
+
+// lines: gamma's ATE_LINES lines, then delta's; c: ml(alpha, beta)
+__global__ void __launch_bounds__(VB_BLOCK) k_vb_miller(const G1A* S, const G1A* A, const G2A* B, const G1A* C, size_t n,
+                                                        const Line* lines, const Fq12* c, Fq12* F) {
+    const size_t j = (size_t)blockIdx.x * VB_BLOCK + threadIdx.x;
+    if (j >= n) return;
+    const G1A s = S[j], a = A[j].neg(), cc = C[j];
+    const G2A q = B[j];
+    const bool live_s = !s.is_inf(), live_c = !cc.is_inf(), live_ab = !a.is_inf() && !q.is_inf();
+    const Line* lg = lines;
+    const Line* ld = lines + ATE_LINES;
+    const Fq2 b3 = twist_b3();
+    G2Proj T{q.x, q.y, Fq2::one()};
+    Fq12 f = Fq12::one();
+    int m = 0;
+    for (int i = ATE_LOOP_BITS - 2; i >= 0; --i) {
+        f = fq12_sqr_ni(f);
+        f = mul_line(f, lg[m], s, live_s);
+        f = mul_line(f, ld[m], cc, live_c);
+        f = mul_line(f, dbl_step(T, b3), a, live_ab);
+        ++m;
+        if (ate_bit(i)) {
+            f = mul_line(f, lg[m], s, live_s);
+            f = mul_line(f, ld[m], cc, live_c);
+            f = mul_line(f, add_step(T, q), a, live_ab);
+            ++m;
+        }
+    }
+    G2A q1, q2;
+    twist_frobenius_pair(q, q1, q2);
+    f = mul_line(f, lg[m], s, live_s);
+    f = mul_line(f, ld[m], cc, live_c);
+    f = mul_line(f, add_step(T, q1), a, live_ab);
+    ++m;
+    f = mul_line(f, lg[m], s, live_s);
+    f = mul_line(f, ld[m], cc, live_c);
+    f = mul_line(f, add_step(T, q2), a, live_ab);
+    F[j] = fq12_mul_ni(f, *c);
+}
+
+__global__ void __launch_bounds__(VB_BLOCK) k_vb_final(const Fq12* F, const int* decoded, size_t n, int* ok) {
+    const size_t j = (size_t)blockIdx.x * VB_BLOCK + threadIdx.x;
+    if (j >= n) return;
+    const bool one = final_exp_exact(F[j]) == Fq12::one();
+    ok[j] = (decoded[j] && one) ? 1 : 0;
+}
+
+// the call's stream and device buffers, kept by the context; a buffer that has to grow is parked until the context goes,
+// because hipFree would wait for every stream of the device (an outstanding proof included)
+struct VerifyBatchState {
+    hipStream_t stream = nullptr;
+    DevBuf<uint8_t> arena;
+    std::vector<DevBuf<uint8_t>> retired;
+    ~VerifyBatchState() {
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+
+static void words_of(const Fq& x, uint64_t* w) {
+    const Fq c = x.to_canonical();
+    for (int i = 0; i < 4; ++i) w[i] = (uint64_t)c.l[2 * i] | ((uint64_t)c.l[2 * i + 1] << 32);
+}
+// a device-resident (Montgomery) CRS point through zk_verify's reader: the same checks, the same point
+static bool check_g1(const G1A& p, G1A& out) {
+    uint64_t w[8];
+    words_of(p.x, w); words_of(p.y, w + 4);
+    return rd_g1(w, out);
+}
+static bool check_g2(const G2A& p, G2A& out) {
+    uint64_t w[16];
+    words_of(p.x.c0, w); words_of(p.x.c1, w + 4); words_of(p.y.c0, w + 8); words_of(p.y.c1, w + 12);
+    return rd_g2(w, out);
+}
+
+}  // namespace zk
+
+using namespace zk;
+
+extern "C" int zk_verify_batch(zk_ctx* ctx, const zk_crs* crs, const uint64_t* inputs, size_t n_inputs, const uint8_t* proofs,
+                               size_t n_proofs, int* ok) {
+    if (!ctx || !crs) return ZK_ERR_ARG;
+    if (n_proofs == 0) return ZK_OK;
+    if (!proofs || !ok || (n_inputs && !inputs)) return ZK_ERR_ARG;
+    std::fill(ok, ok + n_proofs, 0);
+    return guarded(ctx, [&] {
+        const size_t l = crs->input, k = std::min(l, n_inputs);
+        // the inputs zk_verify reads, before anything is launched
+        for (size_t j = 0; j < n_proofs; ++j)
+            for (size_t i = 0; i < k; ++i) {
+                Fr x;
+                const uint64_t* w = inputs + (j * n_inputs + i) * 4;
+                for (int h = 0; h < 4; ++h) { x.l[2 * h] = (uint32_t)w[h]; x.l[2 * h + 1] = (uint32_t)(w[h] >> 32); }
+                ZK_REQUIRE(x.raw_in_range(), ZK_ERR_RANGE, "verify_batch: input >= r");
+            }
+        if (!ctx->verify_batch) ctx->verify_batch = std::make_shared<VerifyBatchState>();
+        VerifyBatchState& st = *ctx->verify_batch;
+        if (!st.stream) ZK_HIP(hipStreamCreateWithFlags(&st.stream, hipStreamNonBlocking));
+        hipStream_t s = st.stream;
+
+        // the CRS points verify reads, copied on this stream (not through crs_download, which runs on the proving stream)
+        G1A h_alpha;
+        G2A h_beta, h_gamma, h_delta;
+        std::vector<G1A> h_sg(k + 1);
+        ZK_HIP(hipMemcpyAsync(&h_alpha, crs->alpha1.p, sizeof(G1A), hipMemcpyDeviceToHost, s));
+        ZK_HIP(hipMemcpyAsync(&h_beta, crs->beta2.p, sizeof(G2A), hipMemcpyDeviceToHost, s));
+        ZK_HIP(hipMemcpyAsync(&h_gamma, crs->gamma2.p, sizeof(G2A), hipMemcpyDeviceToHost, s));
+        ZK_HIP(hipMemcpyAsync(&h_delta, crs->delta2.p, sizeof(G2A), hipMemcpyDeviceToHost, s));
+        ZK_HIP(hipMemcpyAsync(h_sg.data(), crs->sum_gamma1.p, (k + 1) * sizeof(G1A), hipMemcpyDeviceToHost, s));
+        ZK_HIP(hipStreamSynchronize(s));
+        G1A alpha;
+        G2A beta, gamma, delta;
+        ZK_REQUIRE(check_g1(h_alpha, alpha) && check_g2(h_beta, beta) && check_g2(h_gamma, gamma) && check_g2(h_delta, delta), ZK_ERR_ARG,
+                   "verify_batch: CRS point not on the curve or outside G2");
+        for (size_t i = 0; i <= k; ++i) {
+            G1A g;
+            ZK_REQUIRE(check_g1(h_sg[i], g), ZK_ERR_ARG, "verify_batch: CRS point not on the curve");
+        }
+        // once per call: c = ml(alpha, beta) and the lines of gamma and delta
+        std::vector<Line> h_lines(2 * ATE_LINES);
+        ml_lines(gamma, h_lines.data());
+        ml_lines(delta, h_lines.data() + ATE_LINES);
+        const Fq12 h_c = ml_proj(alpha, beta);
+
+        // one arena: constants, then the per-proof arrays of one chunk
+        const size_t m_max = std::min(n_proofs, (size_t)ZK_VERIFY_BATCH_CHUNK);
+        auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+        const size_t o_lines = 0, o_c = o_lines + up(h_lines.size() * sizeof(Line)), o_proofs = o_c + up(sizeof(Fq12));
+        const size_t o_x = o_proofs + up(m_max * ZK_PROOF_BYTES), o_A = o_x + up(m_max * k * 32), o_B = o_A + up(m_max * sizeof(G1A));
+        const size_t o_C = o_B + up(m_max * sizeof(G2A)), o_S = o_C + up(m_max * sizeof(G1A)), o_F = o_S + up(m_max * sizeof(G1A));
+        const size_t o_dec = o_F + up(m_max * sizeof(Fq12)), o_ok = o_dec + up(m_max * sizeof(int)), total = o_ok + up(m_max * sizeof(int));
+        if (st.arena.n < total) {
+            if (st.arena.p) st.retired.push_back(std::move(st.arena));
+            st.arena.alloc(total);
+        }
+        uint8_t* base = st.arena.p;
+        Line* d_lines = (Line*)(base + o_lines);
+        Fq12* d_c = (Fq12*)(base + o_c);
+        uint8_t* d_proofs = base + o_proofs;
+        uint64_t* d_x = (uint64_t*)(base + o_x);
+        G1A *d_A = (G1A*)(base + o_A), *d_C = (G1A*)(base + o_C), *d_S = (G1A*)(base + o_S);
+        G2A* d_B = (G2A*)(base + o_B);
+        Fq12* d_F = (Fq12*)(base + o_F);
+        int *d_dec = (int*)(base + o_dec), *d_ok = (int*)(base + o_ok);
+        ZK_HIP(hipMemcpyAsync(d_lines, h_lines.data(), h_lines.size() * sizeof(Line), hipMemcpyHostToDevice, s));
+        ZK_HIP(hipMemcpyAsync(d_c, &h_c, sizeof(Fq12), hipMemcpyHostToDevice, s));
+
+        std::vector<uint64_t> packed;
+        for (size_t j0 = 0; j0 < n_proofs; j0 += m_max) {
+            const size_t m = std::min(m_max, n_proofs - j0);
+            const unsigned grid = ceil_div(m, VB_BLOCK);
+            ZK_HIP(hipMemcpyAsync(d_proofs, proofs + j0 * ZK_PROOF_BYTES, m * ZK_PROOF_BYTES, hipMemcpyHostToDevice, s));
+            if (k) {
+                const uint64_t* src = inputs + j0 * n_inputs * 4;
+                if (k != n_inputs) {   // only the first k inputs of a row are read (zip truncation)
+                    packed.resize(m * k * 4);
+                    for (size_t j = 0; j < m; ++j) std::memcpy(&packed[j * k * 4], src + j * n_inputs * 4, k * 32);
+                    src = packed.data();
+                }
+                ZK_HIP(hipMemcpyAsync(d_x, src, m * k * 32, hipMemcpyHostToDevice, s));
+            }
+            hipLaunchKernelGGL(k_vb_decode, dim3(grid), dim3(VB_BLOCK), 0, s, d_proofs, m, d_A, d_B, d_C, d_dec);
+            ZK_HIP(hipGetLastError());
+            hipLaunchKernelGGL(k_vb_inputs, dim3(grid), dim3(VB_BLOCK), 0, s, d_x, k, crs->sum_gamma1.p, m, d_S);
+            ZK_HIP(hipGetLastError());
+            hipLaunchKernelGGL(k_vb_miller, dim3(grid), dim3(VB_BLOCK), 0, s, d_S, d_A, d_B, d_C, m, d_lines, d_c, d_F);
+            ZK_HIP(hipGetLastError());
+            hipLaunchKernelGGL(k_vb_final, dim3(grid), dim3(VB_BLOCK), 0, s, d_F, d_dec, m, d_ok);
+            ZK_HIP(hipGetLastError());
+            ZK_HIP(hipMemcpyAsync(ok + j0, d_ok, m * sizeof(int), hipMemcpyDeviceToHost, s));
+            ZK_HIP(hipStreamSynchronize(s));   // also keeps `packed` and the arena's chunk arrays free for the next chunk
+        }
+    });
+}

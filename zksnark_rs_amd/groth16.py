@@ -79,6 +79,12 @@ def verify(sigma, inputs, proof):
     return sigmag1.ctx.verify(sigmag1.crs, inputs, proof)
 
 
+def verify_batch(sigma, inputs, proofs):
+    """verify for many proofs over one CRS on the GPU: inputs[j] (the same count for every j) against proofs[j] -> bool array"""
+    sigmag1, sigmag2 = sigma
+    return sigmag1.ctx.verify_batch(sigmag1.crs, inputs, proofs)
+
+
 def weights(code, inputs):
     """circuit::weights (circuit/mod.rs:529-637)."""
     return Circuit(code).weights(inputs)
