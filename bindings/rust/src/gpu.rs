@@ -68,6 +68,8 @@ extern "C" {
     fn zk_verify(ctx: *mut ZkCtx, crs: *const ZkCrs, inputs: *const u64, n_inputs: usize, proof: *const u8, ok: *mut c_int) -> c_int;
     fn zk_verify_batch(ctx: *mut ZkCtx, crs: *const ZkCrs, inputs: *const u64, n_inputs: usize, proofs: *const u8, n_proofs: usize,
                        ok: *mut c_int) -> c_int;
+    fn zk_verify_batch_all(ctx: *mut ZkCtx, crs: *const ZkCrs, inputs: *const u64, n_inputs: usize, proofs: *const u8, n_proofs: usize,
+                           z: *const u64, ok: *mut c_int) -> c_int;
     // a stream of proofs: witnesses in page-locked host memory, two tickets in flight
     fn zk_host_alloc(bytes: usize, out: *mut *mut c_void) -> c_int;
     fn zk_host_free(p: *mut c_void);
@@ -545,6 +547,23 @@ impl GpuProver {
         let mut ok = vec![0 as c_int; proofs.len()];
         unsafe { check(self.ctx.0, zk_verify_batch(self.ctx.0, self.crs, x.as_ptr(), k, bytes.as_ptr(), proofs.len(), ok.as_mut_ptr())); }
         ok.into_iter().map(|v| v == 1).collect()
+    }
+    /// one verdict for many proofs on the GPU (zk_verify_batch_all): true iff every proof decodes and the random linear
+    /// combination of their pairing equations holds, with secret multipliers z_j = the low 128 bits of FrLocal::random_elem()
+    /// (redrawn when 0); a batch with a bad proof passes with probability at most 1 / (2^128 - 1)
+    pub fn verify_batch_all(&self, inputs: &[Vec<FrLocal>], proofs: &[Proof<G1Local, G2Local>]) -> bool {
+        assert!(inputs.len() == proofs.len(), "one input row per proof");
+        let k = inputs.first().map_or(0, |r| r.len());
+        assert!(inputs.iter().all(|r| r.len() == k), "every proof needs the same number of inputs");
+        let x: Vec<u64> = inputs.iter().flat_map(|r| frs(r)).collect();
+        let bytes: Vec<u8> = proofs.iter().flat_map(|p| proof_to_bytes(p).to_vec()).collect();
+        let z: Vec<u64> = proofs.iter().flat_map(|_| loop {
+            let w = fr_to_words(&FrLocal::random_elem());
+            if w[0] | w[1] != 0 { break [w[0], w[1]]; }
+        }).collect();
+        let mut ok: c_int = 0;
+        unsafe { check(self.ctx.0, zk_verify_batch_all(self.ctx.0, self.crs, x.as_ptr(), k, bytes.as_ptr(), proofs.len(), z.as_ptr(), &mut ok)); }
+        ok == 1
     }
     /// Many proofs over one circuit: the 32 m-byte transfer of witness k+1 overlaps the inner products of proof k
     /// (zk_prove_submit_host / zk_prove_wait with two tickets in flight and page-locked staging buffers).

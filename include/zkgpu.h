@@ -450,6 +450,26 @@ int zk_verify(zk_ctx* ctx, const zk_crs* crs, const uint64_t* inputs, size_t n_i
  * disturbed. */
 #define ZK_VERIFY_BATCH_CHUNK 65536
 int zk_verify_batch(zk_ctx* ctx, const zk_crs* crs, const uint64_t* inputs, size_t n_inputs, const uint8_t* proofs, size_t n_proofs, int* ok);
+/* One verdict for a whole batch on the GPU, by a random linear combination: *ok = 1 iff every proof passes zk_verify's
+ * decoder (tag rules, coordinates < q, on the curve, [r]B = infinity) and
+ *     prod_j e(A_j, B_j)^{z_j} = e(alpha, beta)^{t_0} e(T_S, gamma) e(T_C, delta),
+ *     t_0 = sum_j z_j, t_i = sum_j z_j x_ji (mod r), T_S = sum_{i=0..k} t_i sum_gamma_i, T_C = sum_j z_j C_j.
+ * inputs and proofs as in zk_verify_batch (only the first min(l, n_inputs) entries of a row are read); z: n_proofs
+ * multipliers of 2 words each, little-endian 128-bit integers, every one non-zero.
+ *  - If zk_verify accepts every proof, *ok = 1 for every admissible z (deterministic).
+ *  - A proof that fails to decode gives *ok = 0 (deterministic).
+ *  - Otherwise *ok = 0 unless z falls in a set of density at most 1 / (2^128 - 1): z must be unpredictable to whoever made
+ *    the proofs (draw it from a secure random source after the proofs are fixed).
+ *  - Which proofs are bad: call zk_verify_batch.
+ * Null ctx / crs / proofs / z / ok, or null inputs with n_inputs > 0: ZK_ERR_ARG.  Any z_j = 0: ZK_ERR_ARG and *ok = 0; an
+ * input >= r among those read: ZK_ERR_RANGE and *ok = 0; both decided on the host before anything is launched.  A CRS point
+ * off its curve or outside G2: ZK_ERR_ARG.  n_proofs == 0: ZK_OK and *ok = 1.  Any n_proofs: the proofs go through the
+ * device ZK_VERIFY_BATCH_CHUNK at a time, partial products and sums carry across chunks on the device, and one final
+ * exponentiation runs per call; the verdict does not depend on the chunking.  Synchronous, on the same stream of its own as
+ * zk_verify_batch: no device-wide synchronisation, an outstanding zk_prove_submit ticket is neither waited for nor disturbed.
+ * Below about one wave per SIMD (N < 65536) both batch calls are bound by one lane's serial chain. */
+int zk_verify_batch_all(zk_ctx* ctx, const zk_crs* crs, const uint64_t* inputs, size_t n_inputs, const uint8_t* proofs,
+                        size_t n_proofs, const uint64_t* z, int* ok);
 /* EllipticEncryptable::pairing (fr.rs:120-122): the optimal ate pairing e(P, Q) as 12 Fq coefficients
  * (48 words) in the order c0.a0.c0, c0.a0.c1, c0.a1.c0, ..., c1.a2.c1 of the tower
  * Fq12 = Fq6[w]/(w^2 - v), Fq6 = Fq2[v]/(v^3 - (9+i)).  Host only; needs no context.  ZK_ERR_RANGE when a coordinate

@@ -307,5 +307,40 @@ inline std::vector<bool> verify_batch(const Context& c, const Sigma& sigma, cons
     return std::vector<bool>(ok.begin(), ok.end());
 }
 
+// one verdict for many proofs over one CRS on the GPU (zk_verify_batch_all): true iff every proof decodes and the random linear
+// combination of their pairing equations with the multipliers z (z[j] = {low, high} words of a non-zero 128-bit integer) holds
+inline bool verify_batch_all_with(const Context& c, const Sigma& sigma, const std::vector<std::vector<FrLocal>>& inputs,
+                                  const std::vector<Proof>& proofs, const std::vector<std::array<uint64_t, 2>>& z) {
+    if (inputs.size() != proofs.size() || z.size() != proofs.size())
+        throw Error(ZK_ERR_ARG, "groth16::verify_batch_all: one input row and one multiplier per proof");
+    const size_t n = proofs.size(), k = n ? inputs[0].size() : 0;
+    // one spare element each: proofs and z must not be null even for an empty batch
+    std::vector<uint64_t> x(n * k * 4), zw(2 * n + 2);
+    std::vector<uint8_t> bytes(n * ZK_PROOF_BYTES + 1);
+    for (size_t j = 0; j < n; ++j) {
+        if (inputs[j].size() != k) throw Error(ZK_ERR_ARG, "groth16::verify_batch_all: every proof needs the same number of inputs");
+        for (size_t i = 0; i < k; ++i) std::copy(inputs[j][i].w.begin(), inputs[j][i].w.end(), x.begin() + (j * k + i) * 4);
+        std::copy(proofs[j].bytes.begin(), proofs[j].bytes.end(), bytes.begin() + j * ZK_PROOF_BYTES);
+        zw[2 * j] = z[j][0];
+        zw[2 * j + 1] = z[j][1];
+    }
+    int ok = 0;
+    c.check(zk_verify_batch_all(c.get(), sigma.get(), k ? x.data() : nullptr, k, bytes.data(), n, zw.data(), &ok),
+            "groth16::verify_batch_all");
+    return ok != 0;
+}
+// the same with z drawn from std::random_device (secret to whoever made the proofs); a batch with a bad proof passes with
+// probability at most 1 / (2^128 - 1)
+inline bool verify_batch_all(const Context& c, const Sigma& sigma, const std::vector<std::vector<FrLocal>>& inputs,
+                             const std::vector<Proof>& proofs) {
+    static thread_local std::random_device rd;
+    std::vector<std::array<uint64_t, 2>> z(proofs.size());
+    for (auto& zj : z)
+        do {
+            for (auto& w : zj) w = ((uint64_t)rd() << 32) | rd();
+        } while (!(zj[0] | zj[1]));
+    return verify_batch_all_with(c, sigma, inputs, proofs, z);
+}
+
 }  // namespace groth16
 }  // namespace zksnark

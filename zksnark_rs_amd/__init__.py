@@ -13,6 +13,7 @@ limbs, G2 affine = 16 limbs, infinity = all zero.
 `zksnark_rs_amd.groth16` mirrors the reference's function names and argument order.
 """
 import ctypes as C
+import os
 
 import numpy as np
 
@@ -513,10 +514,9 @@ class Context:
         self._check(self.lib.zk_verify(self.ptr, crs.ptr, a.ctypes.data_as(_lib.u64p), a.shape[0], pb.ctypes.data_as(_lib.u8p), C.byref(ok)))
         return bool(ok.value)
 
-    def verify_batch(self, crs, inputs, proofs):
-        """zk_verify_batch: verify on the GPU for every proof j -> (N,) bool array, entry j == verify(crs, inputs[j], proofs[j]).
-        inputs: (N, k) ints or (N, k, 4) limbs, the same k for every proof; proofs: a list of 259-byte strings or an (N, 259)
-        uint8 array."""
+    @staticmethod
+    def _batch_args(inputs, proofs, name):
+        """(inputs as (N, k, 4) uint64, proofs as (N, 259) uint8) for the batch verify calls"""
         if isinstance(proofs, np.ndarray):
             pb = np.ascontiguousarray(proofs, dtype=np.uint8).reshape(-1, PROOF_BYTES)
         else:
@@ -528,14 +528,48 @@ class Context:
             rows = [[int(x) for x in r] for r in inputs]
             k = len(rows[0]) if rows else 0
             if any(len(r) != k for r in rows):
-                raise ValueError("verify_batch: every proof needs the same number of inputs")
+                raise ValueError("%s: every proof needs the same number of inputs" % name)
             a = ints_to_limbs([x for r in rows for x in r]).reshape(len(rows), k, 4)
         if a.shape[0] != n or a.shape[2:] != (4,):
-            raise ValueError("verify_batch: inputs must hold one row per proof")
+            raise ValueError("%s: inputs must hold one row per proof" % name)
+        return a, pb
+
+    def verify_batch(self, crs, inputs, proofs):
+        """zk_verify_batch: verify on the GPU for every proof j -> (N,) bool array, entry j == verify(crs, inputs[j], proofs[j]).
+        inputs: (N, k) ints or (N, k, 4) limbs, the same k for every proof; proofs: a list of 259-byte strings or an (N, 259)
+        uint8 array."""
+        a, pb = self._batch_args(inputs, proofs, "verify_batch")
+        n = pb.shape[0]
         ok = np.zeros(n, dtype=np.int32)
         self._check(self.lib.zk_verify_batch(self.ptr, crs.ptr, a.ctypes.data_as(_lib.u64p) if a.size else None, a.shape[1],
                                              pb.ctypes.data_as(_lib.u8p), n, ok.ctypes.data_as(C.POINTER(C.c_int))))
         return ok.astype(bool)
+
+    def verify_batch_all(self, crs, inputs, proofs, z=None):
+        """zk_verify_batch_all: one verdict for the whole batch -> True iff every proof decodes and the random linear combination
+        of their pairing equations with multipliers z holds (inputs and proofs as in verify_batch).  z: N non-zero 128-bit
+        multipliers (ints, or an (N, 2) uint64 array of little-endian words); None draws them from os.urandom.  A batch with
+        a bad proof passes only for z in a set of density <= 1 / (2^128 - 1), so z must be secret to whoever made the proofs."""
+        a, pb = self._batch_args(inputs, proofs, "verify_batch_all")
+        n = pb.shape[0]
+        if z is None:
+            zw = np.frombuffer(os.urandom(16 * n), dtype=np.uint64).reshape(n, 2).copy()
+            for j in np.flatnonzero((zw == 0).all(axis=1)):
+                while not zw[j].any():
+                    zw[j] = np.frombuffer(os.urandom(16), dtype=np.uint64)
+        elif isinstance(z, np.ndarray) and z.ndim == 2:
+            zw = np.ascontiguousarray(z, dtype=np.uint64)
+        else:
+            zs = [int(v) for v in z]
+            if any(v < 0 or v >> 128 for v in zs):
+                raise ValueError("verify_batch_all: every z_j is a 128-bit integer")
+            zw = np.array([[v & (2**64 - 1), v >> 64] for v in zs], dtype=np.uint64).reshape(-1, 2)
+        if zw.shape[0] != n:
+            raise ValueError("verify_batch_all: z must hold one multiplier per proof")
+        ok = C.c_int(0)
+        self._check(self.lib.zk_verify_batch_all(self.ptr, crs.ptr, a.ctypes.data_as(_lib.u64p) if a.size else None, a.shape[1],
+                                                 pb.ctypes.data_as(_lib.u8p), n, zw.ctypes.data_as(_lib.u64p), C.byref(ok)))
+        return bool(ok.value)
 
     # ---- profiling ----
     def profile_reset(self):

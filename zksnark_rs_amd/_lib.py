@@ -164,6 +164,7 @@ SIGNATURES = {
     "zk_mgpu_last_error": (C.c_char_p, [C.c_void_p]),
     "zk_verify": (C.c_int, [C.c_void_p, C.c_void_p, u64p, C.c_size_t, u8p, C.POINTER(C.c_int)]),
     "zk_verify_batch": (C.c_int, [C.c_void_p, C.c_void_p, u64p, C.c_size_t, u8p, C.c_size_t, C.POINTER(C.c_int)]),
+    "zk_verify_batch_all": (C.c_int, [C.c_void_p, C.c_void_p, u64p, C.c_size_t, u8p, C.c_size_t, u64p, C.POINTER(C.c_int)]),
     "zk_pairing": (C.c_int, [u64p, u64p, u64p]),
     "zk_profile_reset": (C.c_int, [C.c_void_p]),
     "zk_profile_count": (C.c_int, [C.c_void_p]),

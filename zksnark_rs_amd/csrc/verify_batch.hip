@@ -12,6 +12,7 @@
 #define ZK_MUL_OUTLINE 1
 #include "pipeline.hpp"
 #include "pairing.cuh"
+#include "verify_batch.hpp"
 
 namespace zk {
 
@@ -90,33 +91,6 @@ __global__ void __launch_bounds__(VB_BLOCK) k_vb_final(const Fq12* F, const int*
     if (j >= n) return;
     const bool one = final_exp_exact(F[j]) == Fq12::one();
     ok[j] = (decoded[j] && one) ? 1 : 0;
-}
-
-// the call's stream and device buffers, kept by the context; a buffer that has to grow is parked until the context goes,
-// because hipFree would wait for every stream of the device (an outstanding proof included)
-struct VerifyBatchState {
-    hipStream_t stream = nullptr;
-    DevBuf<uint8_t> arena;
-    std::vector<DevBuf<uint8_t>> retired;
-    ~VerifyBatchState() {
-        if (stream) (void)hipStreamDestroy(stream);
-    }
-};
-
-static void words_of(const Fq& x, uint64_t* w) {
-    const Fq c = x.to_canonical();
-    for (int i = 0; i < 4; ++i) w[i] = (uint64_t)c.l[2 * i] | ((uint64_t)c.l[2 * i + 1] << 32);
-}
-// a device-resident (Montgomery) CRS point through zk_verify's reader: the same checks, the same point
-static bool check_g1(const G1A& p, G1A& out) {
-    uint64_t w[8];
-    words_of(p.x, w); words_of(p.y, w + 4);
-    return rd_g1(w, out);
-}
-static bool check_g2(const G2A& p, G2A& out) {
-    uint64_t w[16];
-    words_of(p.x.c0, w); words_of(p.x.c1, w + 4); words_of(p.y.c0, w + 8); words_of(p.y.c1, w + 12);
-    return rd_g2(w, out);
 }
 
 }  // namespace zk

@@ -85,6 +85,13 @@ def verify_batch(sigma, inputs, proofs):
     return sigmag1.ctx.verify_batch(sigmag1.crs, inputs, proofs)
 
 
+def verify_batch_all(sigma, inputs, proofs):
+    """one verdict for many proofs over one CRS on the GPU: True iff verify would accept every proof (random linear
+    combination with secret multipliers drawn from os.urandom; a false pass has probability <= 1 / (2^128 - 1))"""
+    sigmag1, sigmag2 = sigma
+    return sigmag1.ctx.verify_batch_all(sigmag1.crs, inputs, proofs)
+
+
 def weights(code, inputs):
     """circuit::weights (circuit/mod.rs:529-637)."""
     return Circuit(code).weights(inputs)
