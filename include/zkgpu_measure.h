@@ -2,8 +2,9 @@
  *
  * Nothing here replaces an interface of the reference (/root/reference has no profiling and no tuning knobs): these are the hooks of
  * bench.py (HIP-event timing of the library's own kernels for the `roofline` object), of tools/ (same-box A/B switches) and of
- * tests/test_lazy29.py (the lazy radix at its limb extremes).  The product library exports the three zk_profile_* functions and
- * zk_lazy29_batch; the tuning KEYS below are accepted only by a library built with -DZK_MEASURE (make -C zksnark_rs_amd/csrc measure;
+ * tests/test_lazy29.py (the lazy radix at its limb extremes) and of tests/test_msm_plan.py (the record of what every inner product
+ * decided from its size).  The product library exports the three zk_profile_* functions and zk_lazy29_batch and answers the
+ * "msm_plan" keys of zk_get_option / zk_set_option described at the end of this file; the tuning KEYS below are accepted only by a library built with -DZK_MEASURE (make -C zksnark_rs_amd/csrc measure;
  * zk_get_option(ctx, "measure_build") == 1) -- the product build answers ZK_ERR_UNSUPPORTED to them.
  *
  * Keys of zk_set_option in a ZK_MEASURE build (defaults are what the product build has compiled in):
@@ -56,6 +57,32 @@ enum { ZK_LAZY_MONT = 0, ZK_LAZY_SQR = 1, ZK_LAZY_MONT_DIFF = 2, ZK_LAZY_NORM = 
        ZK_LAZY_FP2_MUL = 7, ZK_LAZY_FP2_SQR = 8 };
 int zk_lazy29_batch(zk_ctx* ctx, int field, int op, const int32_t* a, const int32_t* b, const int32_t* c, const int32_t* d, size_t n,
                     uint64_t* out, int32_t* raw_out);
+
+
+/* ------------------------------------------------------------------------------------------
+ * The plan record: what every inner product since the last reset decided from its size (csrc/msm_impl.hpp, msm_run) -- a few host
+ * stores per product, nothing on the device.  It adds no entry point: it is read through the option calls of zkgpu.h, in the
+ * product build as well (the tests run against that build).
+ *   zk_set_option(ctx, "msm_plan_reset", 0)          empties the record
+ *   zk_get_option(ctx, "msm_plan_count")             products recorded
+ *   zk_get_option(ctx, "msm_plan.<i>.<field>")       one field of product i (decimal), -1 for an unknown field or index
+ * Product i is the i-th in the order the host enqueued them (a proof: A, B in G2, the merged L + H product; with merge_lh = 0: L, A,
+ * B, H).  A product without valid scalars launches nothing and is not recorded.  The record keeps the first 4096 products after a
+ * reset; tests/msm_plan_model.py restates the rules and the GPU tests compare the two.  Fields:
+ *   g2            0 = G1, 1 = G2
+ *   n_used        scalars of the product (all groups of a batch together: groups x the longest group)
+ *   groups        proofs of a batch that share the product (1 otherwise)
+ *   c             window size of the table
+ *   windows_owned how many of its floor(254 / c) + 1 windows this call sums (all of them unless ranks share the windows)
+ *   buckets       2^(c-1) per group (a bucket-range shard: this rank's share)
+ *   run_len       T: longest run of the bucket accumulation
+ *   run_branch    the rule that set T: ZK_MSM_RUN_PLAIN (msm_run_entries as it stands), _WHOLE (one run per bucket: 128 or 256),
+ *                 _FILL (as long as one round of accumulation lanes allows), _SMALL (few entries: 4 .. 28)
+ *   quad_tail     1: merge and reduction tail with four lanes per addition (at most msm_quad_buckets buckets), 0: one lane
+ *   unchained     1: too few lanes to fill the chip, the accumulation does not wait for the previous product's
+ *   cu_count      compute units the rules were evaluated with
+ * ---------------------------------------------------------------------------------------- */
+enum { ZK_MSM_RUN_PLAIN = 0, ZK_MSM_RUN_WHOLE = 1, ZK_MSM_RUN_FILL = 2, ZK_MSM_RUN_SMALL = 3 };
 
 #ifdef __cplusplus
 }

@@ -582,3 +582,14 @@ class Context:
             self.lib.zk_profile_entry(self.ptr, i, C.byref(name), C.byref(ms), C.byref(cnt), C.byref(by))
             out[name.value.decode()] = dict(total_ms=ms.value, launches=cnt.value, algo_bytes=by.value)
         return out
+
+    # ---- the plan record (zkgpu_measure.h: the "msm_plan" option keys) ----
+    MSM_PLAN_FIELDS = ("n_used", "g2", "groups", "c", "windows_owned", "buckets", "run_len", "run_branch", "quad_tail", "unchained", "cu_count")
+
+    def msm_plan_reset(self):
+        self.set_option("msm_plan_reset", 0)
+
+    def msm_plans(self):
+        """What every inner product since the last msm_plan_reset decided from its size: a list of dicts with the fields
+        zkgpu_measure.h lists, in the order the host enqueued the products."""
+        return [{f: self.get_option("msm_plan.%d.%s" % (i, f)) for f in self.MSM_PLAN_FIELDS} for i in range(self.get_option("msm_plan_count"))]

@@ -1,6 +1,7 @@
 // capi.hip -- the extern "C" surface declared in include/zkgpu.h.
 // Nothing here computes on the CPU: every entry point either launches HIP kernels or fails
 // with a status code (ZK_ERR_NO_DEVICE when no GPU is visible).
+#include <cstdio>
 #include <cstring>
 #include <vector>
 #include "kernels.hpp"
@@ -162,10 +163,33 @@ int zk_set_option(zk_ctx* ctx, const char* key, long value) {
     // tools/rccl_starvation.py can price the reservation on one GPU
     if (!std::strcmp(key, "apply_cu_reserve")) return guarded(ctx, [&] { zk::ctx_reserve_cus(ctx, (int)value); });
 #endif
+    if (!std::strcmp(key, "msm_plan_reset")) { ctx->msm_plans.clear(); return ZK_OK; }   // the plan record (zkgpu_measure.h)
     long* s = option_slot(ctx, key);
     if (!s) return ZK_ERR_UNSUPPORTED;
     *s = value;
     return ZK_OK;
+}
+// the plan record, read through zk_get_option: "msm_plan_count", "msm_plan.<i>.<field>" (zkgpu_measure.h); -1 for anything else.
+// tests/test_msm_plan.py reads the order of the strcmp lines below from this text: it must stay the field order of zkgpu_measure.h.
+static long msm_plan_value(const zk_ctx* ctx, const char* key) {
+    if (!std::strcmp(key, "msm_plan_count")) return (long)ctx->msm_plans.size();
+    unsigned long i = 0;
+    int used = 0;
+    if (std::sscanf(key, "msm_plan.%lu.%n", &i, &used) != 1 || used == 0 || i >= ctx->msm_plans.size()) return -1;
+    const MsmPlan& p = ctx->msm_plans[i];
+    const char* f = key + used;
+    if (!std::strcmp(f, "n_used")) return (long)p.n_used;
+    if (!std::strcmp(f, "g2")) return p.g2;
+    if (!std::strcmp(f, "groups")) return p.groups;
+    if (!std::strcmp(f, "c")) return p.c;
+    if (!std::strcmp(f, "windows_owned")) return p.owned;
+    if (!std::strcmp(f, "buckets")) return p.buckets;
+    if (!std::strcmp(f, "run_len")) return p.T;
+    if (!std::strcmp(f, "run_branch")) return p.branch;
+    if (!std::strcmp(f, "quad_tail")) return p.quad;
+    if (!std::strcmp(f, "unchained")) return p.unchained;
+    if (!std::strcmp(f, "cu_count")) return p.cu_count;
+    return -1;
 }
 long zk_get_option(const zk_ctx* ctx, const char* key) {
     if (!ctx || !key) return -1;
@@ -176,6 +200,7 @@ long zk_get_option(const zk_ctx* ctx, const char* key) {
         return 0;
 #endif
     }
+    if (!std::strcmp(key, "msm_plan_count") || !std::strncmp(key, "msm_plan.", 9)) return msm_plan_value(ctx, key);
     long* s = option_slot(const_cast<zk_ctx*>(ctx), key);
     return s ? *s : -1;
 }

@@ -96,6 +96,13 @@ struct PendingEvent {
     int slot;     // in-flight proof the launch belongs to (-1: none)
 };
 
+// What msm_run decided for one product (include/zkgpu_measure.h: the "msm_plan" option keys): host values only, nothing the device reads.
+struct MsmPlan {
+    uint64_t n_used;
+    uint32_t g2, groups, c, owned, buckets, T, branch, quad, unchained, cu_count;
+};
+constexpr size_t MSM_PLAN_CAP = 4096;   // the record keeps the first 4096 products after a reset (a proof has three or four)
+
 struct NttTables;  // ntt.hip
 struct MsmWorkspace;  // kernels.hpp
 struct ProveState;    // prove.hip
@@ -139,6 +146,7 @@ struct zk_ctx {
     long opt_interp_large_log = 20; // interp.hip: trees of at least 2^this elements per level take the form that halves the upward transforms
     long opt_quad_buckets = 65536; // inner products of at most this many buckets run their reduction tail with four lanes per addition (msm_quad.hpp)
     std::map<std::string, zk::ProfEntry> prof;
+    std::vector<zk::MsmPlan> msm_plans;   // one entry per msm_run since the last "msm_plan_reset" (at most MSM_PLAN_CAP)
     std::vector<zk::PendingEvent> pending;
     std::vector<hipEvent_t> event_pool;
     std::map<unsigned, std::shared_ptr<zk::NttTables>> ntt_tables;

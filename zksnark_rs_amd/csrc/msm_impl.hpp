@@ -745,19 +745,22 @@ hipStream_t msm_run(zk_ctx* ctx, MsmWorkspace& ws, hipStream_t st, const MsmTabl
     // the chip 1 / N of its lanes, so its buckets are cut into runs like a small product's -- ms per proof and rank at N = 2 / 4 / 8:
     // 5.77 / 4.06 / 3.20 -> 5.51 / 3.65 / 2.75, profiles/r6_experiments.txt item 6)
     const bool whole = entries_est / (size_t)buckets <= (size_t)std::max<long>(ctx->opt_run_whole, 0) && (size_t)buckets >= fill && !bshard;
-    if (whole) T = entries_est / (size_t)buckets <= 64 ? 128 : RUN_MAX;
+    uint32_t branch = ZK_MSM_RUN_PLAIN;   // which rule set T (the plan record)
+    if (whole) { T = entries_est / (size_t)buckets <= 64 ? 128 : RUN_MAX; branch = ZK_MSM_RUN_WHOLE; }
     else if (ctx->opt_run_fill && entries_est / T > (size_t)(g2 ? 2 : 3) * 256 * (size_t)ctx->cu_count) {
         // More runs than the chip holds lanes (3 waves per SIMD in G1, 2 in G2): every run beyond a bucket's first costs a full
         // XYZZ + XYZZ addition in the merge, so the runs are made as long as one round of lanes allows.  The A product of a 2^20-gate
         // proof (c = 17: 240 entries per bucket): T = 80 instead of 32, 2 merges per bucket instead of 7 (round 5).
         const size_t lanes = (size_t)(g2 ? 2 : 3) * 256 * (size_t)ctx->cu_count;
         T = (uint32_t)std::min<size_t>(RUN_MAX, (entries_est / lanes + 3) & ~(size_t)3);
+        branch = ZK_MSM_RUN_FILL;
     }
-    else if (fill && entries_est / T < fill) T = (uint32_t)std::max<size_t>(4, std::min<size_t>(T, entries_est / fill) & ~(size_t)3);
+    else if (fill && entries_est / T < fill) { T = (uint32_t)std::max<size_t>(4, std::min<size_t>(T, entries_est / fill) & ~(size_t)3); branch = ZK_MSM_RUN_SMALL; }
     // upper bounds: a bucket of z entries has ceil(z / T) <= 1 + z / T runs, of which all but the first take an extra image slot
     const size_t max_extra = entries / T + 1, max_runs = std::min<size_t>((size_t)buckets, entries) + max_extra;
     // an accumulation that cannot fill the chip (3 waves per SIMD = 196608 lanes) is not chained behind the previous one
-    if (std::min(max_runs, entries_est / std::min<size_t>(T, 32) + 1) < (size_t)std::max<long>(ctx->opt_unchain_lanes, 0)) acc_wait = nullptr;
+    const bool unchained = std::min(max_runs, entries_est / std::min<size_t>(T, 32) + 1) < (size_t)std::max<long>(ctx->opt_unchain_lanes, 0);
+    if (unchained) acc_wait = nullptr;
     // rows x columns of the bucket index for the final weighted sum (see k_msm_fold)
     const int kbits = cb / 2, K = 1 << kbits, rows = bpg >> kbits;   // ceil((cb - 1) / 2) column bits
     const int wgs_w = (K + rows + TAIL_THREADS - 1) / TAIL_THREADS;
@@ -768,6 +771,9 @@ hipStream_t msm_run(zk_ctx* ctx, MsmWorkspace& ws, hipStream_t st, const MsmTabl
     // the weighted terms, their sum): those take the quad form too.  Stand-alone at 2^20 gates the weights of the G2 product took 0.81 ms
     // and its final sum 0.39 with one lane per addition.
     const bool quad_end = ctx->opt_quad_buckets > 0;
+    if (ctx->msm_plans.size() < MSM_PLAN_CAP)
+        ctx->msm_plans.push_back(MsmPlan{(uint64_t)n_used, g2 ? 1u : 0u, (uint32_t)groups, (uint32_t)c, (uint32_t)owned, (uint32_t)buckets, T, branch,
+                                         quad ? 1u : 0u, unchained ? 1u : 0u, (uint32_t)ctx->cu_count});
     constexpr size_t QUAD_FOLD_JOBS = 16384;   // fold passes of at most this many output images
     const int run_wgs = (int)ceil_div(buckets, 256);
 
