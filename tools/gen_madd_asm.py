@@ -17,6 +17,8 @@ madd-2008-s addition is one statement whose multipliers work IN PLACE:
   * Y3 = R (Q - X3) - Y PPP needs one negated operand.  The bodies alternate instead: the EVEN body computes
     R (X3 - Q) + Y PPP = -Y3 and leaves the accumulator as (X3, -Y3, ZZ3, ZZZ3); the ODD body starts from that (R = S2 + N,
     N = -Y) and computes R (Q - X3) + N PPP = +Y3.  No negation is ever executed; a run that ends after an even body negates once.
+    S2 + N is a SUM of two normal forms (limbs up to 2^30 - 2, too wide to be squared): the odd body forms it recentred, every low
+    limb 2^29 lower and the limb above one higher -- v_add3_u32 with a constant, still one instruction per limb.
   * the test "same x" (PP == 0 mod p) is a two-compare filter on limb 0 of PP; only when a lane of the wave passes it the exact
     comparison (with 0 and with p: PP is a Montgomery output in (-p/4, 1.3 p), whose normal form is unique) runs, and then the same
     for R^2.  A lane with PP == 0 computes garbage in place; the caller rebuilds its accumulator from the affine point alone
@@ -36,6 +38,7 @@ from gen_mont_asm import FQ, M29, column_range, model, s32, s64, value   # noqa:
 
 ACC = "v[4:5]"
 ACC_LO = "v4"
+RC = (-(1 << 29), 1 - (1 << 29))       # recentring of the odd body's R = S2 + N: limb 0, limbs 1..7 (limb 8 takes the last unit)
 
 
 class Prog:
@@ -168,7 +171,13 @@ def gen_madd_g1(odd):
     mul_inplace(q, QY, ZZZ, QY, M, movlo=False)          # S2 = y2 ZZZ
     for i in range(9):
         src = QY[i] if i < 8 else "ACC"
-        q.emit("add" if odd else "sub", QY[i], src, Y[i])   # R = S2 - Y  (odd: the register holds -Y)
+        if odd:
+            # R = S2 + N (the register holds N = -Y).  Two normal forms ADD up to limbs of 2^30 - 2, and R is squared: eight products of
+            # 2^60 in column 7 (and 2^59 + 2^58 + 2^58 per index in R D + N PPP) pass 2^63.  The same value with every low limb moved
+            # down by 2^29 and the unit handed to the limb above: limbs in [-2^29, 2^29), one instruction per limb as before.
+            q.emit("add3", QY[i], src, Y[i], "rc%d" % (0 if i == 0 else 1) if i < 8 else 1)
+        else:
+            q.emit("sub", QY[i], src, Y[i])             # R = S2 - Y
     sqr_inplace(q, QX, PP, M, XB)                        # PP = P^2 (doubled limbs on XB, which is free until R^2)
     exact_zero(q, PP, "z", "s1", "s2", M)
     mul_inplace(q, XA, PP, XA, M)                        # Q = X PP
@@ -207,6 +216,7 @@ def simulate(q, regs_in, P29, INV29):
     for i in range(9):
         r["p%d" % i] = P29[i]
     r["inv"] = INV29
+    r["rc0"], r["rc1"] = RC
     acc = None
     masks = {}
 
@@ -244,6 +254,8 @@ def simulate(q, regs_in, P29, INV29):
             r[ins[1]] = s32(val(ins[2]) + val(ins[3]))
         elif op == "lshl1_add":
             r[ins[1]] = s32((val(ins[2]) << 1) + val(ins[3]))
+        elif op == "add3":
+            r[ins[1]] = s32(val(ins[2]) + val(ins[3]) + val(ins[4]))
         elif op == "cmp_eq":
             masks[ins[1]] = (val(ins[2]) & 0xffffffff) == (val(ins[3]) & 0xffffffff)
         elif op == "s_and":
@@ -448,6 +460,8 @@ def render(q, name, groups_io, groups_out, doc):
             lines.append("v_add_u32 %s, %s, %s" % (reg(ins[1]), reg(ins[2]), reg(ins[3])))
         elif op == "lshl1_add":
             lines.append("v_lshl_add_u32 %s, %s, 1, %s" % (reg(ins[1]), reg(ins[2]), reg(ins[3])))
+        elif op == "add3":
+            lines.append("v_add3_u32 %s, %s, %s, %s" % (reg(ins[1]), reg(ins[2]), reg(ins[3]), reg(ins[4])))
         elif op == "cmp_eq":
             lines.append("v_cmp_eq_u32_e64 %s, %s, %s" % (reg(ins[1]), reg(ins[2]), reg(ins[3])))
         elif op == "s_and":
@@ -490,6 +504,8 @@ def render(q, name, groups_io, groups_out, doc):
     outs += ['[z] "=&s"(z)', '[z2] "=&s"(z2)', '[s1] "=&s"(s1)', '[s2] "=&s"(s2)']
     inps = ['[p%d] "s"((int32_t)PR::P29[%d])' % (i, i) for i in range(9)]
     inps += ['[inv] "s"((int32_t)PR::INV29)', '[mask] "s"(0x1fffffff)']
+    if any(i[0] == "add3" for i in q.ins):
+        inps += ['[rc0] "s"(%d)' % RC[0], '[rc1] "s"(%d)' % RC[1]]
     o.append("        : " + ", ".join(outs))
     o.append("        : " + ", ".join(inps))
     o.append('        : "vcc", "scc", "v4", "v5");')
@@ -510,7 +526,8 @@ HEADER = """// madd_asm.inc -- GENERATED by tools/gen_madd_asm.py; do not edit.
 DOC_E = """// EVEN body: (XA, Y, ZZ, ZZZ) += (QX, QY).  Out: X3 in XB, -Y3 (!) in Y, ZZ3, ZZZ3 in place; XA, QX, QY are clobbered.
 // same_x: lanes whose point has the accumulator's x (their outputs are garbage: the sum is 2 P or infinity); same_point: of those, the
 // lanes with the same y."""
-DOC_O = """// ODD body: the accumulator's Y register holds -Y (what the even body leaves).  Out: X3 in XB, +Y3 in Y, ZZ3, ZZZ3 in place."""
+DOC_O = """// ODD body: the accumulator's Y register holds -Y (what the even body leaves).  Out: X3 in XB, +Y3 in Y, ZZ3, ZZZ3 in place.
+// R = S2 + (-Y) adds two normal forms: it is recentred (low limbs - 2^29, the unit to the limb above) so that |limb| <= 2^29 when it is squared."""
 
 
 def write(path):

@@ -1,6 +1,8 @@
 // quad_check.hip -- quad29.cuh against lazy29.cuh on the GPU: the four-lane addition / doubling / small multiple of random points
 // must equal the one-lane forms (compared as Jacobian images through xyzz_store, which is canonical per representation, so both are
 // brought to affine x Z-independent form: X/ZZ, Y/ZZZ cross-multiplied).
+// A diagnostic: the suite carries these assertions now (tests/test_gpu_point_forms.py runs the quad forms at the limb bounds against
+// the published formulas, lane against lane, and on curve points); this program stays for its round-by-round k_diag view.
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -I zksnark_rs_amd/csrc tools/quad_check.hip -o /tmp/quad_check && /tmp/quad_check
 #include <hip/hip_runtime.h>
 #include <cstdio>

@@ -403,6 +403,8 @@ ZK_HD bool madd_lazy(JacR<F>& p, const typename LazyOf<F>::type& qx, const typen
 // 1674 for the Jacobian form.  Over Fq2 the four coordinates take 72 registers: the kernel sits at the
 // 256-register limit with 16 dwords of scratch, and is still 6 % faster than the Jacobian accumulator.
 // L = FpR<..> (G1) or Fp2R<..> (G2).
+// Value ranges every XYZZ form keeps, per component (pinned at their corners by tests/test_gpu_point_forms.py): X3 = norm(RR - PPP - 2Q)
+// in (-4.15 p, 2.05 p); Y in (-3 p, 3 p) over Fq (mont_diff) and in (-1.55 p, 1.55 p) over Fq2 (two products); ZZ, ZZZ in (-p/4, 1.3 p).
 template <class L>
 struct XyzzR {
     L X, Y, ZZ, ZZZ;
@@ -632,6 +634,7 @@ ZK_HD Jac<F> jacr_store(const JacR<F>& p) {
 }
 
 // dbl-2009-l (a = 0) with every intermediate kept multipliable (see the bounds in the header)
+// From a canonical load or one dbl_lazy / add_lazy on such: D in (-5.7 p, 3.6 p), X3 in (-7.45 p, 12.7 p), Y3 in (-10.65 p, 3.3 p), Z3 in (-p/2, 2.6 p).
 template <class F>
 ZK_HD JacR<F> dbl_lazy(const JacR<F>& p) {
     typedef typename LazyOf<F>::type L;
