@@ -70,6 +70,18 @@ extern "C" {
                        ok: *mut c_int) -> c_int;
     fn zk_verify_batch_all(ctx: *mut ZkCtx, crs: *const ZkCrs, inputs: *const u64, n_inputs: usize, proofs: *const u8, n_proofs: usize,
                            z: *const u64, ok: *mut c_int) -> c_int;
+    // the .zk front end's witness as a compiled tape: one witness on the host, or a whole batch on the GPU with the witnesses left in
+    // HBM where zk_prove_batch_submit takes them (d_weights_out + j * m * 32 bytes is witness j)
+    fn zk_circuit_parse(code: *const c_char, out: *mut *mut ZkCircuit, err: *mut c_char, err_len: usize) -> c_int;
+    fn zk_circuit_free(c: *mut ZkCircuit);
+    fn zk_circuit_dims(c: *const ZkCircuit, m: *mut usize, n: *mut usize, input: *mut usize, n_in: *mut usize) -> c_int;
+    fn zk_circuit_last_error(c: *const ZkCircuit) -> *const c_char;
+    fn zk_circuit_tape_dims(c: *const ZkCircuit, ops: *mut usize, slots: *mut usize, consts: *mut usize, depth: *mut usize,
+                            width: *mut usize) -> c_int;
+    fn zk_circuit_weights_tape(c: *const ZkCircuit, inputs: *const u64, n_in: usize, weights_out: *mut u64, m: usize) -> c_int;
+    fn zk_witgen_create(ctx: *mut ZkCtx, c: *const ZkCircuit, out: *mut *mut ZkWitgen) -> c_int;
+    fn zk_witgen_free(w: *mut ZkWitgen);
+    fn zk_witgen_run(w: *mut ZkWitgen, d_inputs: *const c_void, n_in: usize, count: usize, d_weights_out: *mut c_void, m: usize) -> c_int;
     // a stream of proofs: witnesses in page-locked host memory, two tickets in flight
     fn zk_host_alloc(bytes: usize, out: *mut *mut c_void) -> c_int;
     fn zk_host_free(p: *mut c_void);
@@ -90,6 +102,8 @@ extern "C" {
     fn zk_mgpu_last_error(p: *const ZkMgpu) -> *const c_char;
 }
 #[repr(C)] pub struct ZkComm { _p: [u8; 0] }
+#[repr(C)] pub struct ZkCircuit { _p: [u8; 0] }
+#[repr(C)] pub struct ZkWitgen { _p: [u8; 0] }
 #[repr(C)] pub struct ZkMgpu { _p: [u8; 0] }
 
 fn check(ctx: *mut ZkCtx, rc: c_int) {

@@ -76,7 +76,8 @@ const char* zk_last_error(const zk_ctx* ctx);          /* detail of the last fai
  * from 2.7 to 2.2 ms, profiles/r4_rccl_starvation.txt), "basis_tree_min" (see zk_crs_upload), "merge_lh" (default 1: the witness
  * product L = sum a_i sum_delta_i and H + r B1 + s A, which only occur added together in the proof element c, are ONE inner product
  * over the table xi_t | xi | sum_delta with one set of buckets and one reduction tail; 0 = two products as in round 4; same proof
- * bytes, +1.3 % proofs/s at 2^20 gates, profiles/r5_experiments.txt item 2).  Each is exercised by a -m gpu test.  Unknown keys are
+ * bytes, +1.3 % proofs/s at 2^20 gates, profiles/r5_experiments.txt item 2), "witgen_scratch_kib" (read by zk_witgen_create: how much
+ * device memory, in KiB, that generator may hold for slot values; default 8388608 = 8 GiB).  Each is exercised by a -m gpu test.  Unknown keys are
  * answered with ZK_ERR_UNSUPPORTED.  Measurement entry points and switches -- kernel event timing, the tuning keys of bench.py --opt /
  * --serialize -- are NOT part of this header: include/zkgpu_measure.h. */
 int zk_set_option(zk_ctx* ctx, const char* key, long value);
@@ -209,11 +210,38 @@ int zk_circuit_rows(const zk_circuit* c, int which, uint64_t* ptr, uint32_t* gat
 /* circuit::weights (circuit/mod.rs:529-637): inputs in `in` order -> [1] ++ wire values (m x 4 words) */
 int zk_circuit_weights(const zk_circuit* c, const uint64_t* inputs, size_t n_in, uint64_t* weights_out, size_t m);
 const char* zk_circuit_last_error(const zk_circuit* c);
+/* zk_circuit_parse also compiles circuit::weights into a flat tape: field operations dst = a (*|+) b or dst = a over numbered slots
+ * (slot 0 = the constant 1, slot i + 1 = the i-th variable of the witness, behind them unused `in` variables and temporaries), operands
+ * a slot or a literal of the constant pool, no slot written twice, sorted by level (1 + the highest level read; inputs and constants
+ * are level 0).  A program whose weights fail for EVERY input (assignment to an assigned variable, an unbound variable, a variable
+ * order that does not cover the wires) still parses; the calls below then return that error, status and text as zk_circuit_weights'. */
+/* assignments-level shape of the program: depth = number of levels when each `=` is one node, width = most `=` in one level;
+ * ops / slots / consts = what the compiled tape holds (any pointer may be NULL).  Returns the stored static error if the program has one. */
+int zk_circuit_tape_dims(const zk_circuit* c, size_t* ops, size_t* slots, size_t* consts, size_t* depth, size_t* width);
+/* zk_circuit_weights through the tape: same arguments, same words out, same status and text on every error; nothing is parsed, no
+ * name is looked up and nothing recurses per call. */
+int zk_circuit_weights_tape(const zk_circuit* c, const uint64_t* inputs, size_t n_in, uint64_t* weights_out, size_t m);
 /* QAP<CoefficientPoly<FrLocal>>::from(root_rep) (fr.rs:140-173; Lagrange interpolation
  * coefficient_poly.rs:159-200) on the GPU for the circuit's roots 1..n -> dense device QAP. */
 int zk_circuit_qap(zk_ctx* ctx, const zk_circuit* c, zk_qap** out);
 /* The same QAP through zk_qap_upload_sparse_integers: no interpolation, no 16384-gate limit, identical proofs. */
 int zk_circuit_qap_sparse(zk_ctx* ctx, const zk_circuit* c, zk_qap** out);
+
+/* Witness generation for a whole batch on the GPU: the tape run with one instance per lane (csrc/witgen.hip). */
+typedef struct zk_witgen zk_witgen;
+/* uploads the circuit's tape and constant pool; the circuit may be freed afterwards, the context must outlive the generator.
+ * Static program error -> that error (zk_last_error has the text). */
+int zk_witgen_create(zk_ctx* ctx, const zk_circuit* c, zk_witgen** out);
+void zk_witgen_free(zk_witgen* w);     /* NULL is a no-op */
+/* circuit::weights for `count` input sets at once.  d_inputs: count x n_in x 4 words, canonical, instance-major (instance j's block is
+ * what zk_circuit_weights takes); d_weights_out: count x m x 4 words, canonical, instance-major, so d_weights_out + j*m*4 words is a
+ * valid d_weights[j] of zk_prove_batch_submit / d_weights of zk_prove_dev.  Both device pointers.  Complete on return.  count == 0:
+ * ZK_OK, nothing touched.  n_in or m not the program's: ZK_ERR_ARG with zk_circuit_weights' text.  An input word pattern >= r in any
+ * instance (unused `in` variables included, as on the host): ZK_ERR_RANGE, found on the device; zk_last_error names the LOWEST such
+ * instance and the contents of d_weights_out are unspecified.  Scratch: slots x 2 KiB per 64 instances in flight, at most the option
+ * "witgen_scratch_kib" -- `count` is not limited by memory (the instances run in chunks), a program of which 64 instances do not fit
+ * gives ZK_ERR_SIZE. */
+int zk_witgen_run(zk_witgen* w, const void* d_inputs, size_t n_in, size_t count, void* d_weights_out, size_t m);
 
 /* ------------------------------------------------------------------------------------------
  * CRS  (SigmaG1 / SigmaG2, groth16/mod.rs:105-121)

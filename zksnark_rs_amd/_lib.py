@@ -104,6 +104,11 @@ SIGNATURES = {
     "zk_circuit_rows": (C.c_int, [C.c_void_p, C.c_int, u64p, u32p, u64p, C.POINTER(C.c_size_t)]),
     "zk_circuit_weights": (C.c_int, [C.c_void_p, u64p, C.c_size_t, u64p, C.c_size_t]),
     "zk_circuit_last_error": (C.c_char_p, [C.c_void_p]),
+    "zk_circuit_tape_dims": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_size_t)] * 5),
+    "zk_circuit_weights_tape": (C.c_int, [C.c_void_p, u64p, C.c_size_t, u64p, C.c_size_t]),
+    "zk_witgen_create": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "zk_witgen_free": (None, [C.c_void_p]),
+    "zk_witgen_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t]),
     "zk_msm_auto_window": (C.c_int, [C.c_size_t]),
     "zk_msm_auto_window_g2": (C.c_int, [C.c_size_t]),
     "zk_circuit_qap": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),

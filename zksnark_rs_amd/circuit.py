@@ -1,7 +1,8 @@
 """The reference's .zk front end behind the C ABI (host code, as in the reference).
 
     ASTParser::try_parse      circuit/mod.rs:224-527   -> Circuit(code)
-    circuit::weights          circuit/mod.rs:529-637   -> Circuit.weights(inputs)
+    circuit::weights          circuit/mod.rs:529-637   -> Circuit.weights(inputs), Circuit.weights_tape(inputs) (compiled tape),
+                                                          Witgen(ctx, circuit).run(...) (the tape for many input sets on the GPU)
     QAP::from(root_rep)       fr.rs:140-173            -> Circuit.qap(ctx)   (Lagrange interpolation on the GPU)
 """
 import ctypes as C
@@ -59,6 +60,23 @@ class Circuit:
             raise ParseErr(self.lib.zk_circuit_last_error(self.ptr).decode())
         return out
 
+    def weights_tape(self, inputs):
+        """weights() through the tape compiled at parse time: same words, same errors, no parsing or name lookup per call."""
+        a = ints_to_limbs(list(inputs)) if not isinstance(inputs, np.ndarray) else np.ascontiguousarray(inputs, dtype=np.uint64)
+        out = np.zeros((self.m, 4), np.uint64)
+        rc = self.lib.zk_circuit_weights_tape(self.ptr, a.ctypes.data_as(_lib.u64p), a.shape[0], out.ctypes.data_as(_lib.u64p), self.m)
+        if rc != 0:
+            raise ParseErr(self.lib.zk_circuit_last_error(self.ptr).decode())
+        return out
+
+    def tape_dims(self):
+        """dict(ops, slots, consts: what the tape holds; depth, width: the program's shape with each `=` as one node)."""
+        v = [C.c_size_t() for _ in range(5)]
+        rc = self.lib.zk_circuit_tape_dims(self.ptr, *[C.byref(x) for x in v])
+        if rc != 0:
+            raise ParseErr(self.lib.zk_circuit_last_error(self.ptr).decode())
+        return dict(zip(("ops", "slots", "consts", "depth", "width"), (x.value for x in v)))
+
     def qap(self, ctx):
         p = C.c_void_p()
         ctx._check(self.lib.zk_circuit_qap(ctx.ptr, self.ptr, C.byref(p)))
@@ -73,6 +91,56 @@ class Circuit:
         q = Qap(ctx, p, self.lib.zk_qap_free)
         q.n, q.m, q.input, q.dense, q.roots = self.n, self.m, self.input, False, "integers"
         return q
+
+
+class Witgen:
+    """zk_witgen_*: circuit::weights for many input sets at once on the GPU (csrc/witgen.hip).  The circuit may be closed afterwards;
+    the context must stay open.  scratch_kib: cap of the device memory held for slot values (None = the context's option
+    "witgen_scratch_kib", 8 GiB by default); the instances run in chunks under it."""
+
+    def __init__(self, ctx, circuit, scratch_kib=None):
+        self.ctx, self.lib = ctx, ctx.lib
+        self.n_in, self.m = circuit.n_in, circuit.m
+        p = C.c_void_p()
+        if scratch_kib is None:
+            rc = self.lib.zk_witgen_create(ctx.ptr, circuit.ptr, C.byref(p))
+        else:
+            keep = ctx.get_option("witgen_scratch_kib")
+            ctx.set_option("witgen_scratch_kib", scratch_kib)
+            try:
+                rc = self.lib.zk_witgen_create(ctx.ptr, circuit.ptr, C.byref(p))
+            finally:
+                ctx.set_option("witgen_scratch_kib", keep)
+        ctx._check(rc)
+        self.ptr = p
+
+    def close(self):
+        if getattr(self, "ptr", None):
+            self.lib.zk_witgen_free(self.ptr)
+            self.ptr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def run(self, d_inputs_ptr, count, d_out_ptr, n_in=None, m=None):
+        """d_inputs_ptr: count x n_in x 4 words in HBM; d_out_ptr: count x m x 4 words, witness j at d_out_ptr + j * m * 32 bytes."""
+        self.ctx._check(self.lib.zk_witgen_run(self.ptr, C.c_void_p(d_inputs_ptr), self.n_in if n_in is None else n_in, count,
+                                               C.c_void_p(d_out_ptr), self.m if m is None else m))
+
+    def run_numpy(self, inputs):
+        """inputs (count, n_in, 4) uint64 -> (count, m, 4) uint64, staged through torch tensors on the context's device."""
+        import torch
+        a = np.ascontiguousarray(inputs, dtype=np.uint64).reshape(-1, self.n_in, 4)
+        count = a.shape[0]
+        dev = "cuda:%d" % self.ctx.device
+        d_in = torch.from_numpy(a.view(np.int64)).to(dev)
+        d_out = torch.empty((count, self.m, 4), dtype=torch.int64, device=dev)
+        torch.cuda.synchronize(dev)
+        self.run(d_in.data_ptr(), count, d_out.data_ptr())
+        return d_out.cpu().numpy().view(np.uint64)
 
 
 def qap_download_dense(ctx, qap):

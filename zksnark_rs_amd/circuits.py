@@ -56,3 +56,12 @@ def chain_weights(log_n, x, avals):
             w[2 * n + 1] = ak
             w[2] = (prev + ak) % R_MODULUS
     return ints_to_limbs(w)
+
+
+def chain_zk(n):
+    """The chain circuit of n >= 2 gates as .zk text (deg_15.zk is chain_zk(16) with other names): inputs x, a1..an in that order;
+    the parser gives the wires of chain_rows, m = 2n + 2."""
+    lines = ["(in x %s)" % " ".join("a%d" % k for k in range(1, n + 1)), "(out y)", "(verify x y)", "(program", "(= t1 (* x a1))"]
+    lines += ["(= t%d (* x (+ t%d a%d)))" % (k, k - 1, k) for k in range(2, n)]
+    lines.append("(= y (* 1 (+ t%d a%d))))" % (n - 1, n))
+    return "\n".join(lines)

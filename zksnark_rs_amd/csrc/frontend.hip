@@ -13,10 +13,12 @@
 // polynomial is one synthetic division t / (X - r_k) scaled by 1 / t'(r_k) (one lane per root), and
 // each wire polynomial is the weighted sum of the bases of its entries -- the same unique
 // interpolating polynomials, so the dense coefficient matrices are identical.
+#include <array>
 #include <map>
 #include <sstream>
 #include <unordered_map>
 #include "pipeline.hpp"
+#include "witgen_tape.hpp"
 
 namespace zk {
 
@@ -181,9 +183,137 @@ struct zk_circuit {
     std::vector<zk::Node> exprs;
     std::vector<std::string> order;    // variable_order (ast.rs:62-83)
     std::string last_error;
+    zk::Tape tape;                     // circuit::weights compiled once (witgen_tape.hpp), or its static error
 };
 
 namespace zk {
+
+// ---- circuit::weights as a tape (witgen_tape.hpp) -----------------------------------------------
+// Walks the program once in the order circuit_weights below does and meets its input-independent errors in the same order; the
+// first one is kept with the reference's status and text in place of the tape.  The program parses either way.
+struct TapeCompiler {
+    struct Unbound {};
+    Tape& t;
+    std::unordered_map<std::string, uint32_t> env;     // variables that have a value so far -> slot
+    std::vector<uint32_t> op_level, slot_level, slot_alevel;   // per op; per slot: tape level / level with each `=` as one node
+    std::map<std::array<uint32_t, 8>, uint32_t> pool;
+    uint32_t amax = 0;                                  // highest `=` level among the variables the current right-hand side reads
+
+    uint32_t fresh() {
+        slot_level.push_back(0);
+        slot_alevel.push_back(0);
+        return (uint32_t)t.slots++;
+    }
+    uint32_t constant(const Fr& v) {
+        std::array<uint32_t, 8> key;
+        for (int i = 0; i < 8; ++i) key[i] = v.l[i];
+        auto it = pool.find(key);
+        if (it == pool.end()) { it = pool.emplace(key, (uint32_t)t.consts.size()).first; t.consts.push_back(v); }
+        return it->second | TAPE_CONST;
+    }
+    uint32_t level_of(uint32_t operand) const { return (operand & TAPE_CONST) ? 0 : slot_level[operand]; }
+    uint32_t emit(uint32_t kind, uint32_t dst, uint32_t a, uint32_t b) {
+        const uint32_t lv = 1 + std::max(level_of(a), kind == TAPE_COPY ? 0u : level_of(b));
+        t.ops.push_back({dst, a, b, kind});
+        op_level.push_back(lv);
+        slot_level[dst] = lv;
+        return dst;
+    }
+    static constexpr uint32_t ANY = 0xffffffffu;
+    // operand holding e's value; writes it to slot `want` where e is an operation (a variable or literal is returned as it is)
+    uint32_t expr(const Node& e, uint32_t want) {
+        switch (e.kind) {
+            case Node::Literal: return constant(e.lit);
+            case Node::Var: {
+                auto it = env.find(e.var);
+                if (it == env.end()) throw Unbound{};
+                amax = std::max(amax, slot_alevel[it->second]);
+                return it->second;
+            }
+            case Node::Mul: {
+                const uint32_t a = expr(e.kids[0], ANY), b = expr(e.kids[1], ANY);
+                return emit(TAPE_MUL, want == ANY ? fresh() : want, a, b);
+            }
+            case Node::Add: {
+                if (e.kids.empty()) return constant(Fr::zero());
+                if (e.kids.size() == 1) return expr(e.kids[0], want);
+                uint32_t acc = expr(e.kids[0], ANY);
+                for (size_t i = 1; i < e.kids.size(); ++i) {
+                    const uint32_t b = expr(e.kids[i], ANY);
+                    acc = emit(TAPE_ADD, (i + 1 == e.kids.size() && want != ANY) ? want : fresh(), acc, b);
+                }
+                return acc;
+            }
+            default: throw Unbound{};
+        }
+    }
+};
+
+static void compile_tape(zk_circuit& c) {
+    Tape& t = c.tape;
+    const auto& ex = c.exprs;
+    t.n_in = ex[0].kids.size();
+    t.m = c.u.size();
+    auto fail = [&](const std::string& msg) {
+        t.status = ZK_ERR_ARG;
+        t.error = msg;
+        t.ops.clear(); t.level_ptr.clear(); t.consts.clear(); t.in_slot.clear();
+        t.slots = t.depth = t.width = 0;
+    };
+    auto serr = [](const char* s) { return std::string("StructureErr(None, ") + s + ")"; };
+    TapeCompiler k{t};
+    // slot 0 = the constant 1, then the witness in its output order; everything else behind
+    std::unordered_map<std::string, uint32_t> out_slot;
+    for (size_t i = 0; i < c.order.size(); ++i) out_slot[c.order[i]] = (uint32_t)(i + 1);
+    t.slots = std::max(t.m, c.order.size() + 1);
+    k.slot_level.assign(t.slots, 0);
+    k.slot_alevel.assign(t.slots, 0);
+    // inputs: a name given twice keeps its last value (env[name] is overwritten), the earlier one is only range-checked
+    std::unordered_map<std::string, size_t> last;
+    for (size_t i = 0; i < t.n_in; ++i) last[ex[0].kids[i].var] = i;
+    for (size_t i = 0; i < t.n_in; ++i) {
+        const std::string& name = ex[0].kids[i].var;
+        auto it = out_slot.find(name);
+        const uint32_t s = (last[name] == i && it != out_slot.end()) ? it->second : k.fresh();
+        t.in_slot.push_back(s);
+        if (last[name] == i) k.env[name] = s;
+    }
+    std::vector<size_t> per_level;
+    for (const auto& a : ex[3].kids) {
+        const std::string& var = a.kids[0].var;
+        if (k.env.count(var)) return fail(serr("Attempted to assign to an already assigned variable"));
+        auto it = out_slot.find(var);
+        const uint32_t dst = it != out_slot.end() ? it->second : k.fresh();   // (every assigned name follows `verify`, so it is in the order)
+        k.amax = 0;
+        try {
+            const uint32_t r = k.expr(a.kids[1], dst);
+            if (r != dst) k.emit(TAPE_COPY, dst, r, 0);
+        } catch (const TapeCompiler::Unbound&) {
+            return fail(serr("Under constrained expression"));
+        }
+        const uint32_t al = k.amax + 1;
+        k.slot_alevel[dst] = al;
+        if (per_level.size() < al) per_level.resize(al, 0);
+        ++per_level[al - 1];
+        k.env[var] = dst;
+    }
+    if (c.order.size() + 1 != t.m) return fail("panic: variable order does not cover every wire");
+    for (const auto& name : c.order)
+        if (!k.env.count(name)) return fail("panic: Every variable should have an assignment");
+    if (t.slots >= TAPE_CONST || t.ops.size() >= TAPE_CONST) return fail("program too large for the witness tape");
+    t.depth = per_level.size();
+    for (size_t n : per_level) t.width = std::max(t.width, n);
+    // stable counting sort of the operations by level
+    uint32_t levels = 0;
+    for (uint32_t lv : k.op_level) levels = std::max(levels, lv);
+    t.level_ptr.assign(levels + 1, 0);
+    for (uint32_t lv : k.op_level) ++t.level_ptr[lv];            // count of level lv at [lv]; [0] stays 0
+    for (uint32_t l = 1; l <= levels; ++l) t.level_ptr[l] += t.level_ptr[l - 1];
+    std::vector<uint32_t> at(t.level_ptr.begin(), t.level_ptr.end());   // at[lv - 1] = next position of level lv
+    std::vector<TapeOp> sorted(t.ops.size());
+    for (size_t i = 0; i < t.ops.size(); ++i) sorted[at[k.op_level[i] - 1]++] = t.ops[i];
+    t.ops.swap(sorted);
+}
 
 static zk_circuit* circuit_parse(const std::string& code) {
     std::unique_ptr<zk_circuit> c(new zk_circuit());
@@ -260,6 +390,7 @@ static zk_circuit* circuit_parse(const std::string& code) {
         }
     }
     c->n_gates = gate;
+    compile_tape(*c);
     return c.release();
 }
 
@@ -315,6 +446,20 @@ static void circuit_weights(const zk_circuit& c, const uint64_t* inputs, size_t 
         if (it == env.end()) throw ParseError{ZK_ERR_ARG, "panic: Every variable should have an assignment"};
         put(i + 1, it->second);
     }
+}
+
+// circuit_weights through the tape: the same checks in the same order, no strings, no recursion, no map per call
+static void circuit_weights_tape(const zk_circuit& c, const uint64_t* inputs, size_t n_in, uint64_t* out, size_t m) {
+    auto serr = [](const std::string& s) { return ParseError{ZK_ERR_ARG, "StructureErr(None, " + s + ")"}; };
+    const Tape& t = c.tape;
+    if (t.n_in != n_in) throw serr("Wrong number of values supplied");
+    if (m != t.m) throw serr("weights buffer size mismatch");
+    for (size_t i = 0; i < n_in; ++i)
+        if (!fr_from_words(inputs + 4 * i).raw_in_range()) throw ParseError{ZK_ERR_RANGE, "input value >= r"};
+    if (t.status) throw ParseError{t.status, t.error};
+    static thread_local std::vector<Fr> vals;
+    if (vals.size() < t.slots) vals.resize(t.slots);
+    tape_run_host(t, inputs, vals.data(), out);
 }
 
 // ---- QAP::from(root_rep) for arbitrary roots on the GPU ----------------------------------------
@@ -471,6 +616,8 @@ static int front_guard(std::string* err, Fn&& fn) {
 
 using namespace zk;
 
+const zk::Tape& zk_circuit_tape(const zk_circuit* c) { return c->tape; }
+
 extern "C" {
 
 int zk_circuit_parse(const char* code, zk_circuit** out, char* err, size_t err_len) {
@@ -516,6 +663,24 @@ int zk_circuit_weights(const zk_circuit* c, const uint64_t* inputs, size_t n_in,
     int rc = front_guard(&msg, [&] { circuit_weights(*c, inputs, n_in, weights_out, m); });
     const_cast<zk_circuit*>(c)->last_error = msg;
     return rc;
+}
+int zk_circuit_weights_tape(const zk_circuit* c, const uint64_t* inputs, size_t n_in, uint64_t* weights_out, size_t m) {
+    if (!c || !weights_out || (n_in && !inputs)) return ZK_ERR_ARG;
+    std::string msg;
+    int rc = front_guard(&msg, [&] { circuit_weights_tape(*c, inputs, n_in, weights_out, m); });
+    const_cast<zk_circuit*>(c)->last_error = msg;
+    return rc;
+}
+int zk_circuit_tape_dims(const zk_circuit* c, size_t* ops, size_t* slots, size_t* consts, size_t* depth, size_t* width) {
+    if (!c) return ZK_ERR_ARG;
+    const Tape& t = c->tape;
+    if (t.status) { const_cast<zk_circuit*>(c)->last_error = t.error; return t.status; }
+    if (ops) *ops = t.ops.size();
+    if (slots) *slots = t.slots;
+    if (consts) *consts = t.consts.size();
+    if (depth) *depth = t.depth;
+    if (width) *width = t.width;
+    return ZK_OK;
 }
 const char* zk_circuit_last_error(const zk_circuit* c) { return c ? c->last_error.c_str() : "null circuit"; }
 

@@ -1,0 +1,202 @@
+// witgen.hip -- zk_witgen_*: circuit::weights (circuit/mod.rs:529-637) for many input sets at once on the GPU.
+//
+// The program's tape (witgen_tape.hpp: single-assignment field operations over numbered slots, sorted by level) is uploaded once.
+// k_witgen runs it with one INSTANCE per lane:
+//   group      64 consecutive instances = one workgroup of W waves; lane l of every wave works on instance 64 g + l
+//   scratch    the group's slot values in HBM, slot-major: value of slot s for lane l at (s * 64 + l), so one wave's access to a slot
+//              is 2 KiB contiguous; slots * 64 * 32 bytes per group in flight
+//   load       inputs range-checked (word pattern >= r: atomicMin of the instance index into a flag word), to Montgomery form, to
+//              their slots -- strided over the W waves
+//   evaluate   level by level; the operations of a level are independent and strided over the W waves, __syncthreads() between
+//              levels when W > 1.  W = 1 (a chain) has one wave per group, program order, no barrier at all.  Either way a wave
+//              requests the operands of its next operation before it computes the current one (witgen_run_ops)
+//   store      slots 0..m-1 to canonical form, instance-major (what zk_prove_dev / zk_prove_batch_submit take per witness)
+// Lanes behind `count` in the last group never return early: they take part in every barrier and are predicated off every load and
+// store.  Groups run in chunks of as many as the scratch cap holds (option "witgen_scratch_kib"), so `count` is not bounded by memory.
+#include "pipeline.hpp"
+#include "witgen_tape.hpp"
+
+struct zk_witgen {
+    zk_ctx* ctx = nullptr;
+    size_t n_in = 0, m = 0, slots = 0, levels = 0;
+    unsigned waves = 1;
+    size_t scratch_cap = 0;                 // bytes
+    zk::DevBuf<zk::TapeOp> ops;
+    zk::DevBuf<uint32_t> level_ptr, in_slot;
+    zk::DevBuf<zk::Fr> consts, scratch;
+    zk::DevBuf<unsigned long long> flag;
+};
+
+namespace zk {
+
+static constexpr int WG_LANES = 64;
+static constexpr unsigned WG_MAX_WAVES = 4;
+static constexpr unsigned long long WG_NO_ERROR = ~0ull;
+
+// The W rule: W = the mean number of operations per level, rounded up to a power of two, at most 4 (and at most the widest level).
+// A level of `width` operations costs ceil(width / W) rounds and every level one barrier; waves beyond the mean width would wait at
+// barriers most of the time, and parallelism beyond one group comes from the other groups.  A chain (every level 1 wide) gets W = 1.
+static unsigned witgen_waves(const Tape& t) {
+    const size_t levels = t.levels();
+    if (!levels) return 1;
+    const size_t mean = (t.ops.size() + levels - 1) / levels;
+    unsigned w = 1;
+    while (w < mean && w < WG_MAX_WAVES) w *= 2;
+    while (w > 1 && w / 2 >= t.max_level_width()) w /= 2;
+    return w;
+}
+
+__device__ __forceinline__ Fr witgen_operand(uint32_t x, const Fr* __restrict__ consts, const Fr* sc) {
+    return (x & TAPE_CONST) ? consts[x & ~TAPE_CONST] : sc[(size_t)x * WG_LANES];
+}
+// Operations begin, begin + stride, ... < end in this order, each reading what the ones before it in the run (and before the run)
+// wrote.  The operands of the next operation are requested BEFORE the current one is computed, so that their memory latency passes
+// under a field multiplication instead of in front of it; where the next operation reads the current result (every step of a chain)
+// the value is handed over in registers and the early load is dropped.  Without this a dependent chain pays store -> load through
+// the cache per operation: 2.8 us per operation measured on the 2^16-gate chain, one wave per group.
+__device__ __forceinline__ void witgen_run_ops(const TapeOp* __restrict__ ops, uint32_t begin, uint32_t end, uint32_t stride,
+                                               const Fr* __restrict__ consts, Fr* sc) {
+    if (begin >= end) return;
+    TapeOp cur = ops[begin];
+    Fr a = witgen_operand(cur.a, consts, sc), b = witgen_operand(cur.b, consts, sc);
+    for (uint32_t k = begin; k < end; k += stride) {
+        const bool more = k + stride < end;
+        TapeOp nxt = cur;
+        Fr na = a, nb = b;
+        if (more) {
+            nxt = ops[k + stride];
+            na = witgen_operand(nxt.a, consts, sc);
+            nb = witgen_operand(nxt.b, consts, sc);
+        }
+        const Fr r = cur.kind == TAPE_COPY ? a : cur.kind == TAPE_MUL ? a * b : a + b;
+        sc[(size_t)cur.dst * WG_LANES] = r;
+        if (!(nxt.a & TAPE_CONST) && nxt.a == cur.dst) na = r;
+        if (!(nxt.b & TAPE_CONST) && nxt.b == cur.dst) nb = r;
+        cur = nxt;
+        a = na;
+        b = nb;
+    }
+}
+
+__global__ void __launch_bounds__(WG_LANES * WG_MAX_WAVES)
+k_witgen(const TapeOp* __restrict__ ops, const uint32_t* __restrict__ level_ptr, unsigned levels, const uint32_t* __restrict__ in_slot,
+         const Fr* __restrict__ consts, const uint64_t* __restrict__ inputs, unsigned n_in, unsigned m, size_t slots, size_t first, size_t count,
+         Fr* __restrict__ scratch, uint64_t* __restrict__ out, unsigned long long* __restrict__ flag) {
+    const unsigned lane = threadIdx.x & (WG_LANES - 1), wave = threadIdx.x / WG_LANES, W = blockDim.x / WG_LANES;
+    const size_t j = first + (size_t)blockIdx.x * WG_LANES + lane;      // instance
+    const bool live = j < count;
+    Fr* sc = scratch + (size_t)blockIdx.x * slots * WG_LANES + lane;    // slot s of this lane: sc[s * 64]
+
+    if (live) {
+        if (wave == 0) sc[0] = Fr::one();
+        const uint64_t* in = inputs + j * (size_t)n_in * 4;
+        for (unsigned i = wave; i < n_in; i += W) {
+            Fr x;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const uint64_t w = in[4 * (size_t)i + k];
+                x.l[2 * k] = (uint32_t)w;
+                x.l[2 * k + 1] = (uint32_t)(w >> 32);
+            }
+            if (!x.raw_in_range()) atomicMin(flag, (unsigned long long)j);
+            sc[(size_t)in_slot[i] * WG_LANES] = Fr::from_canonical(x);
+        }
+    }
+    if (W > 1) __syncthreads();
+
+    if (W == 1) {                       // one wave, program order: the whole tape as one run, no barrier
+        if (live) witgen_run_ops(ops, 0, level_ptr[levels], 1, consts, sc);
+    } else {
+        for (unsigned l = 0; l < levels; ++l) {
+            if (live) witgen_run_ops(ops, level_ptr[l] + wave, level_ptr[l + 1], W, consts, sc);
+            __syncthreads();
+        }
+    }
+
+    if (live) {
+        uint64_t* o = out + j * (size_t)m * 4;
+        for (unsigned i = wave; i < m; i += W) {
+            const Fr x = sc[(size_t)i * WG_LANES].to_canonical();
+#pragma unroll
+            for (int k = 0; k < 4; ++k) o[4 * (size_t)i + k] = (uint64_t)x.l[2 * k] | ((uint64_t)x.l[2 * k + 1] << 32);
+        }
+    }
+}
+
+static zk_witgen* witgen_create(zk_ctx* ctx, const Tape& t) {
+    ZK_REQUIRE(!t.status, t.status, t.error);
+    ZK_REQUIRE(t.n_in < (1u << 31) && t.m < (1u << 31), ZK_ERR_SIZE, "witgen: program too large");
+    std::unique_ptr<zk_witgen> w(new zk_witgen());
+    w->ctx = ctx;
+    w->n_in = t.n_in; w->m = t.m; w->slots = t.slots; w->levels = t.levels();
+    w->waves = witgen_waves(t);
+    w->scratch_cap = (size_t)std::max<long>(ctx->opt_witgen_scratch_kib, 0) * 1024;
+    hipStream_t st = ctx->stream;
+    auto up = [&](auto& buf, const auto& host) {
+        buf.alloc(std::max<size_t>(host.size(), 1));   // never a null array
+        if (!host.empty()) ZK_HIP(hipMemcpyAsync(buf.p, host.data(), host.size() * sizeof(host[0]), hipMemcpyHostToDevice, st));
+    };
+    up(w->ops, t.ops);
+    up(w->in_slot, t.in_slot);
+    up(w->consts, t.consts);
+    const std::vector<uint32_t> lp = t.level_ptr.empty() ? std::vector<uint32_t>{0} : t.level_ptr;
+    up(w->level_ptr, lp);
+    w->flag.alloc(1);
+    ZK_HIP(hipStreamSynchronize(st));   // the host vectors may go away with the circuit
+    return w.release();
+}
+
+static void witgen_run(zk_witgen& w, const void* d_inputs, size_t count, void* d_out) {
+    zk_ctx* ctx = w.ctx;
+    hipStream_t st = ctx->stream;
+    const size_t group_bytes = w.slots * WG_LANES * sizeof(Fr);
+    const size_t groups = (count + WG_LANES - 1) / WG_LANES;
+    const size_t fit = w.scratch_cap / group_bytes;
+    ZK_REQUIRE(fit >= 1, ZK_ERR_SIZE, "witgen: one group of 64 instances needs " + std::to_string(group_bytes >> 10) +
+                                          " KiB of scratch, more than the option witgen_scratch_kib allows");
+    const size_t chunk = std::min(std::min(groups, fit), (size_t)1 << 30);
+    w.scratch.ensure(chunk * w.slots * WG_LANES);
+    const unsigned long long none = WG_NO_ERROR;
+    ZK_HIP(hipMemcpyAsync(w.flag.p, &none, sizeof(none), hipMemcpyHostToDevice, st));
+    for (size_t g0 = 0; g0 < groups; g0 += chunk) {      // same stream: a chunk starts when the one before has left the scratch
+        const size_t g = std::min(chunk, groups - g0);
+        ProfScope ps(ctx, "witgen", 0.0);
+        hipLaunchKernelGGL(k_witgen, dim3((unsigned)g), dim3(WG_LANES * w.waves), 0, st, w.ops.p, w.level_ptr.p, (unsigned)w.levels, w.in_slot.p,
+                           w.consts.p, (const uint64_t*)d_inputs, (unsigned)w.n_in, (unsigned)w.m, w.slots, g0 * WG_LANES, count, w.scratch.p,
+                           (uint64_t*)d_out, w.flag.p);
+        ZK_HIP(hipGetLastError());
+    }
+    unsigned long long bad = WG_NO_ERROR;
+    ZK_HIP(hipMemcpyAsync(&bad, w.flag.p, sizeof(bad), hipMemcpyDeviceToHost, st));
+    ZK_HIP(hipStreamSynchronize(st));
+    ZK_REQUIRE(bad == WG_NO_ERROR, ZK_ERR_RANGE, "witgen: input value >= r in instance " + std::to_string(bad));
+}
+
+}  // namespace zk
+
+using namespace zk;
+
+extern "C" {
+
+int zk_witgen_create(zk_ctx* ctx, const zk_circuit* c, zk_witgen** out) {
+    if (!ctx || !c || !out) return ZK_ERR_ARG;
+    *out = nullptr;
+    return guarded(ctx, [&] { *out = witgen_create(ctx, zk_circuit_tape(c)); });
+}
+void zk_witgen_free(zk_witgen* w) {
+    if (!w) return;
+    (void)hipSetDevice(w->ctx->device);
+    delete w;
+}
+int zk_witgen_run(zk_witgen* w, const void* d_inputs, size_t n_in, size_t count, void* d_weights_out, size_t m) {
+    if (!w) return ZK_ERR_ARG;
+    return guarded(w->ctx, [&] {
+        ZK_REQUIRE(n_in == w->n_in, ZK_ERR_ARG, "StructureErr(None, Wrong number of values supplied)");
+        ZK_REQUIRE(m == w->m, ZK_ERR_ARG, "StructureErr(None, weights buffer size mismatch)");
+        if (count == 0) return;
+        ZK_REQUIRE(d_weights_out && (d_inputs || !n_in), ZK_ERR_ARG, "witgen: null device pointer");
+        witgen_run(*w, d_inputs, count, d_weights_out);
+    });
+}
+
+}  // extern "C"
