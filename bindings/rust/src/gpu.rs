@@ -48,6 +48,10 @@ pub struct ZkCrsOut {                                    // zk_crs_out (same fie
 pub struct ZkSparseRows { ptr: *const u64, gate: *const u32, val: *const u64 }   // zk_sparse_rows: CSR by wire
 #[repr(C)]
 pub struct ZkQapSparseDesc { log_n: c_uint, m: usize, input: usize, u: ZkSparseRows, v: ZkSparseRows, w: ZkSparseRows }
+#[repr(C)]
+pub struct ZkQapCheckResult { pub bad_gates: u32, pub first_bad: u32, pub flags: u32 }   // zk_qap_check_result (12 bytes)
+pub const ZK_QAP_CHECK_NONE: u32 = 0xFFFF_FFFF;
+pub const ZK_QAP_CHECK_WIRE0: u32 = 1;
 
 extern "C" {
     fn zk_ctx_create(device: c_int, out: *mut *mut ZkCtx) -> c_int;
@@ -82,6 +86,10 @@ extern "C" {
     fn zk_witgen_create(ctx: *mut ZkCtx, c: *const ZkCircuit, out: *mut *mut ZkWitgen) -> c_int;
     fn zk_witgen_free(w: *mut ZkWitgen);
     fn zk_witgen_run(w: *mut ZkWitgen, d_inputs: *const c_void, n_in: usize, count: usize, d_weights_out: *mut c_void, m: usize) -> c_int;
+    // does a witness satisfy the QAP (sparse forms)?  One witness on the host, or `count` of them where zk_witgen_run left them
+    fn zk_qap_check(ctx: *mut ZkCtx, qap: *const ZkQap, weights: *const u64, m: usize, out: *mut ZkQapCheckResult) -> c_int;
+    fn zk_qap_check_dev(ctx: *mut ZkCtx, qap: *const ZkQap, d_weights: *const c_void, m: usize, stride: usize, count: usize,
+                        out: *mut ZkQapCheckResult) -> c_int;
     // a stream of proofs: witnesses in page-locked host memory, two tickets in flight
     fn zk_host_alloc(bytes: usize, out: *mut *mut c_void) -> c_int;
     fn zk_host_free(p: *mut c_void);
@@ -544,6 +552,27 @@ impl GpuProver {
     }
     pub fn prove(&self, weights: &[FrLocal]) -> Proof<G1Local, G2Local> {
         self.prove_with_rs(weights, FrLocal::random_elem(), FrLocal::random_elem())
+    }
+    /// What the reference lacks: (number of gates with U_j V_j != W_j, the lowest such gate, weights[0] == 1), decided on the GPU
+    /// (zk_qap_check) before a proof is spent on the witness.  Sparse forms only (from_root_rep*): the dense form of
+    /// GpuProver::new holds coefficients, not its roots, and panics with the library's "unsupported" text.
+    pub fn check_witness(&self, weights: &[FrLocal]) -> (usize, Option<usize>, bool) {
+        let w = frs(weights);
+        let mut res = ZkQapCheckResult { bad_gates: 0, first_bad: ZK_QAP_CHECK_NONE, flags: 0 };
+        unsafe { check(self.ctx.0, zk_qap_check(self.ctx.0, self.qap, w.as_ptr(), weights.len(), &mut res)); }
+        (res.bad_gates as usize, if res.first_bad == ZK_QAP_CHECK_NONE { None } else { Some(res.first_bad as usize) },
+         res.flags & ZK_QAP_CHECK_WIRE0 == 0)
+    }
+    /// true iff prove(weights) yields a proof that verify accepts: every gate holds and the constant wire is 1
+    pub fn is_satisfied(&self, weights: &[FrLocal]) -> bool {
+        let (bad, _, wire0_ok) = self.check_witness(weights);
+        bad == 0 && wire0_ok
+    }
+    /// the same for `count` witnesses resident on the device, m elements each, `stride` elements apart (zk_witgen_run's layout: stride == m)
+    pub fn check_witnesses_dev(&self, d_weights: *const c_void, m: usize, stride: usize, count: usize) -> Vec<ZkQapCheckResult> {
+        let mut out: Vec<ZkQapCheckResult> = (0..count).map(|_| ZkQapCheckResult { bad_gates: 0, first_bad: ZK_QAP_CHECK_NONE, flags: 0 }).collect();
+        unsafe { check(self.ctx.0, zk_qap_check_dev(self.ctx.0, self.qap, d_weights, m, stride, count, out.as_mut_ptr())); }
+        out
     }
     /// groth16::verify against the device CRS
     pub fn verify(&self, inputs: &[FrLocal], proof: &Proof<G1Local, G2Local>) -> bool {

@@ -77,7 +77,8 @@ const char* zk_last_error(const zk_ctx* ctx);          /* detail of the last fai
  * product L = sum a_i sum_delta_i and H + r B1 + s A, which only occur added together in the proof element c, are ONE inner product
  * over the table xi_t | xi | sum_delta with one set of buckets and one reduction tail; 0 = two products as in round 4; same proof
  * bytes, +1.3 % proofs/s at 2^20 gates, profiles/r5_experiments.txt item 2), "witgen_scratch_kib" (read by zk_witgen_create: how much
- * device memory, in KiB, that generator may hold for slot values; default 8388608 = 8 GiB).  Each is exercised by a -m gpu test.  Unknown keys are
+ * device memory, in KiB, that generator may hold for slot values; default 8388608 = 8 GiB), "qap_check_chunk" and
+ * "qap_check_by_instance" (see zk_qap_check).  Each is exercised by a -m gpu test.  Unknown keys are
  * answered with ZK_ERR_UNSUPPORTED.  Measurement entry points and switches -- kernel event timing, the tuning keys of bench.py --opt /
  * --serialize -- are NOT part of this header: include/zkgpu_measure.h. */
 int zk_set_option(zk_ctx* ctx, const char* key, long value);
@@ -192,6 +193,45 @@ int zk_qap_kind(const zk_qap* qap);
  * j + 1, j < n), u and v only (the prover never evaluates W).  4 words per element, canonical; weights beyond m_qap are ignored. */
 int zk_qap_weighted_sum(zk_ctx* ctx, const zk_qap* qap, const uint64_t* weights, size_t m, int which, uint64_t* out);
 int zk_qap_download_dense(zk_ctx* ctx, const zk_qap* qap, uint64_t* u, uint64_t* v, uint64_t* w, uint64_t* t);
+
+/* Does a witness satisfy the QAP, and if not, where?  groth16::prove drops the remainder of (U V - W) / t (mod.rs:233-253,277), so a
+ * witness that breaks a constraint still yields 259 well-formed bytes that zk_verify rejects; this is the is_satisfied /
+ * which_is_unsatisfied the reference lacks, as a call of its own -- no zk_prove* entry point runs it.
+ *  - Gate values: U_j = sum_i a_i u_i(root_j) over the entries of gate j (0-based gate index = row of the root representation),
+ *    V_j and W_j alike; duplicate (wire, gate) entries add up, as everywhere else.  Gate j is bad when U_j V_j != W_j (mod r).
+ *  - Only wires i < min(m, m_qap) contribute, because zip(weights) truncates (mod.rs:233-253): the answer is about what zk_prove* does
+ *    with exactly these arguments.  A short witness is legal, its missing wires count as 0.  Words behind min(m, m_qap) and the
+ *    padding between instances (stride > m) are never read and may hold anything.
+ *  - Satisfied means bad_gates == 0 && flags == 0.  ZK_QAP_CHECK_WIRE0: the constant wire is not 1 (or there is no weight at all); then
+ *    every gate may hold and zk_verify still rejects the proof.
+ *  - The three sparse forms (zk_qap_kind 0, 2, 3) are supported; the roots never enter, only the rows by gate.  The dense form (kind 1)
+ *    gives ZK_ERR_UNSUPPORTED: it holds coefficients and t, not its roots, so no gate can be named -- zk_circuit_qap_sparse is the
+ *    way in for .zk circuits.
+ *  - An element >= r among the min(m, m_qap) read of any instance: ZK_ERR_RANGE, found on the device; zk_last_error names the LOWEST
+ *    such instance and `out` is unspecified.
+ *  - count == 0: ZK_OK, nothing touched.  Null ctx / qap / out, null weights with m > 0, stride < m, a QAP of another context:
+ *    ZK_ERR_ARG.
+ *  - Synchronous, on a stream of its own as the batch verifiers are, no device-wide synchronisation: an outstanding
+ *    zk_prove_submit ticket is neither waited for nor disturbed.  U, V and W are never written to memory.  The first check of a QAP
+ *    builds W's rows by gate (36 bytes per entry of w; the prover never needs them) and keeps them with the handle.
+ *  - Any count: the instances go through the device in chunks of at most "qap_check_chunk" (instance, gate) pairs per launch (option,
+ *    default ZK_QAP_CHECK_CHUNK_LANES; at least one instance per launch); the results do not depend on the chunking.  Option
+ *    "qap_check_by_instance" (default 0: consecutive lanes take consecutive gates of one instance; 1: consecutive lanes take the same
+ *    gate of consecutive instances -- the other mapping of the A/B in DESIGN 4h, kept as the cross-check of the first). */
+#define ZK_QAP_CHECK_NONE 0xFFFFFFFFu
+#define ZK_QAP_CHECK_WIRE0 1u    /* flags: weights[0] != 1 (or no weights at all) */
+#define ZK_QAP_CHECK_CHUNK_LANES (1u << 28)
+typedef struct {
+    uint32_t bad_gates;   /* number of gates j with U_j * V_j != W_j (mod r) */
+    uint32_t first_bad;   /* lowest such j, ZK_QAP_CHECK_NONE if none */
+    uint32_t flags;       /* ZK_QAP_CHECK_WIRE0 */
+} zk_qap_check_result;
+/* one witness in host memory */
+int zk_qap_check(zk_ctx* ctx, const zk_qap* qap, const uint64_t* weights, size_t m, zk_qap_check_result* out);
+/* `count` witnesses in DEVICE memory, witness j at d_weights + j * stride * 32 bytes, m elements each (stride >= m; stride == m is
+ * zk_witgen_run's output layout); out: `count` results in HOST memory.  Complete on return. */
+int zk_qap_check_dev(zk_ctx* ctx, const zk_qap* qap, const void* d_weights, size_t m, size_t stride, size_t count,
+                     zk_qap_check_result* out);
 
 /* ------------------------------------------------------------------------------------------
  * .zk front end (the input side of the path; host code, as in the reference)

@@ -14,6 +14,7 @@
 //   groth16::setup(&qap) -> (SigmaG1, SigmaG2)  (mod.rs:134-197)   zksnark::groth16::setup(ctx, qap) -> Sigma
 //   groth16::prove(&qap, (&s1, &s2), &weights)  (mod.rs:213-296)   zksnark::groth16::prove(ctx, qap, sigma, weights)
 //   groth16::verify((s1, s2), &inputs, proof)   (mod.rs:299-320)   zksnark::groth16::verify(ctx, sigma, inputs, proof)
+//   (none: prove drops the remainder, mod.rs:277)                  zksnark::groth16::is_satisfied / which_is_unsatisfied(ctx, qap, weights)
 //
 // Where the reference panics (division by zero fr.rs:54,69; "Dividend must be non-zero" field/mod.rs:440;
 // unwrap() of a ParseErr) this API throws zksnark::Error carrying the ABI status and message.  The
@@ -22,6 +23,7 @@
 #pragma once
 #include <array>
 #include <cstdint>
+#include <optional>
 #include <random>
 #include <stdexcept>
 #include <string>
@@ -156,6 +158,13 @@ class QAP {
         c.check(zk_circuit_qap(c.get(), circuit.get(), &q), "QAP::from");
         return QAP(q);
     }
+    // the same QAP kept as rows over the roots 1..n (zk_circuit_qap_sparse): no interpolation, any size, identical proofs; the form
+    // groth16::is_satisfied / which_is_unsatisfied take
+    static QAP from_sparse(const Context& c, const Circuit& circuit) {
+        zk_qap* q = nullptr;
+        c.check(zk_circuit_qap_sparse(c.get(), circuit.get(), &q), "QAP::from_sparse");
+        return QAP(q);
+    }
     // the struct literal QAP { u, v, w, t, input, degree }: u, v, w = m polynomials of `degree` coefficients
     // (shorter ones are zero padded), t = degree + 1 coefficients
     static QAP from_dense(const Context& c, const std::vector<std::vector<FrLocal>>& u, const std::vector<std::vector<FrLocal>>& v,
@@ -280,6 +289,24 @@ inline Proof prove_with(const Context& c, const QAP& qap, const Sigma& sigma, co
 // groth16::prove(&qap, (&sigma_g1, &sigma_g2), &weights) (mod.rs:213-296): r, s drawn inside (mod.rs:231)
 inline Proof prove(const Context& c, const QAP& qap, const Sigma& sigma, const std::vector<FrLocal>& weights_) {
     return prove_with(c, qap, sigma, weights_, FrLocal::random_elem(), FrLocal::random_elem());
+}
+
+// What the reference lacks (prove drops the remainder of (U V - W) / t, mod.rs:277): the witness against the QAP on the GPU, before a
+// proof is spent on it (zk_qap_check).  Sparse QAP forms (QAP::from_sparse, QAP::from_root_rep); the dense form throws ZK_ERR_UNSUPPORTED.
+inline zk_qap_check_result check(const Context& c, const QAP& qap, const std::vector<FrLocal>& weights_) {
+    zk_qap_check_result r{};
+    c.check(zk_qap_check(c.get(), qap.get(), weights_.empty() ? nullptr : weights_[0].w.data(), weights_.size(), &r), "groth16::is_satisfied");
+    return r;
+}
+// true iff prove(c, qap, sigma, weights) yields a proof that verify accepts: every gate holds and weights[0] == 1
+inline bool is_satisfied(const Context& c, const QAP& qap, const std::vector<FrLocal>& weights_) {
+    const zk_qap_check_result r = check(c, qap, weights_);
+    return r.bad_gates == 0 && r.flags == 0;
+}
+// the lowest gate (0-based row of the root representation) with U_j V_j != W_j; nullopt when every gate holds
+inline std::optional<size_t> which_is_unsatisfied(const Context& c, const QAP& qap, const std::vector<FrLocal>& weights_) {
+    const zk_qap_check_result r = check(c, qap, weights_);
+    return r.first_bad == ZK_QAP_CHECK_NONE ? std::nullopt : std::optional<size_t>(r.first_bad);
 }
 
 // groth16::verify((sigma_g1, sigma_g2), &inputs, proof) (mod.rs:299-320)

@@ -354,6 +354,26 @@ class Context:
         self._check(self.lib.zk_qap_weighted_sum(self.ptr, qap.ptr, wp, w.shape[0], which, out.ctypes.data_as(_lib.u64p)))
         return out
 
+    QAP_CHECK_DTYPE = np.dtype([("bad_gates", np.uint32), ("first_bad", np.uint32), ("flags", np.uint32)])
+
+    def qap_check(self, qap, weights):
+        """zk_qap_check: does the witness satisfy the (sparse) QAP?  -> (bad_gates, first_bad or None, wire0_ok): the number of gates
+        with U_j V_j != W_j, the lowest such gate (0-based), and whether weights[0] == 1.  Satisfied = (0, None, True).  Only the
+        first min(len(weights), m_qap) weights are read, as by prove."""
+        w, wp = _u64(np.asarray(weights, dtype=np.uint64).reshape(-1, 4))
+        out = _lib.QapCheckResult()
+        self._check(self.lib.zk_qap_check(self.ptr, qap.ptr, wp if w.shape[0] else None, w.shape[0], C.byref(out)))
+        return int(out.bad_gates), (None if out.first_bad == _lib.QAP_CHECK_NONE else int(out.first_bad)), not (out.flags & _lib.QAP_CHECK_WIRE0)
+
+    def qap_check_dev(self, qap, d_ptr, m, count, stride=None):
+        """zk_qap_check_dev: `count` witnesses of m elements in device memory, witness j at d_ptr + j * stride * 32 bytes (stride = m
+        when None: Witgen.run's layout) -> structured array (QAP_CHECK_DTYPE) of `count` results; first_bad is QAP_CHECK_NONE
+        (0xFFFFFFFF) where every gate holds."""
+        out = np.zeros(count, dtype=self.QAP_CHECK_DTYPE)
+        self._check(self.lib.zk_qap_check_dev(self.ptr, qap.ptr, C.c_void_p(d_ptr), m, m if stride is None else stride, count,
+                                              out.ctypes.data_as(C.POINTER(_lib.QapCheckResult))))
+        return out
+
     def qap_save(self, qap, path):
         """Write the QAP container (zk_qap_save): sparse rows or dense matrices."""
         self._check(self.lib.zk_qap_save(self.ptr, qap.ptr, str(path).encode()))

@@ -17,6 +17,9 @@ PROOF_BYTES = 259
 PARTIAL_BYTES = 768
 MAX_IN_FLIGHT = 4      # ZK_MAX_IN_FLIGHT
 MAX_BATCH = 64          # ZK_MAX_BATCH
+QAP_CHECK_NONE = 0xFFFFFFFF     # ZK_QAP_CHECK_NONE
+QAP_CHECK_WIRE0 = 1             # ZK_QAP_CHECK_WIRE0
+QAP_CHECK_CHUNK_LANES = 1 << 28  # ZK_QAP_CHECK_CHUNK_LANES
 
 u64p = C.POINTER(C.c_uint64)
 u32p = C.POINTER(C.c_uint32)
@@ -44,6 +47,10 @@ class CrsOut(C.Structure):
     _fields_ = [("alpha_g1", u64p), ("beta_g1", u64p), ("delta_g1", u64p), ("xi_g1", u64p),
                 ("sum_gamma_g1", u64p), ("sum_delta_g1", u64p), ("xi_t_g1", u64p),
                 ("beta_g2", u64p), ("gamma_g2", u64p), ("delta_g2", u64p), ("xi_g2", u64p)]
+
+
+class QapCheckResult(C.Structure):
+    _fields_ = [("bad_gates", C.c_uint32), ("first_bad", C.c_uint32), ("flags", C.c_uint32)]
 
 
 # zk_comm_ops / zk_mgpu_backend: tables of C callbacks (tests plug gloo and CPU stand-ins in here)
@@ -98,6 +105,8 @@ SIGNATURES = {
     "zk_qap_kind": (C.c_int, [C.c_void_p]),
     "zk_qap_weighted_sum": (C.c_int, [C.c_void_p, C.c_void_p, u64p, C.c_size_t, C.c_int, u64p]),
     "zk_qap_download_dense": (C.c_int, [C.c_void_p, C.c_void_p, u64p, u64p, u64p, u64p]),
+    "zk_qap_check": (C.c_int, [C.c_void_p, C.c_void_p, u64p, C.c_size_t, C.POINTER(QapCheckResult)]),
+    "zk_qap_check_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(QapCheckResult)]),
     "zk_circuit_parse": (C.c_int, [C.c_char_p, C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t]),
     "zk_circuit_free": (None, [C.c_void_p]),
     "zk_circuit_dims": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),

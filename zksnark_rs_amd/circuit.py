@@ -130,6 +130,12 @@ class Witgen:
         self.ctx._check(self.lib.zk_witgen_run(self.ptr, C.c_void_p(d_inputs_ptr), self.n_in if n_in is None else n_in, count,
                                                C.c_void_p(d_out_ptr), self.m if m is None else m))
 
+    def run_checked(self, qap, d_inputs_ptr, count, d_out_ptr):
+        """run(), then zk_qap_check_dev on the witnesses where they lie: the structured result array of Context.qap_check_dev, one
+        entry per instance.  The witnesses never visit the host.  qap: a sparse QAP of this circuit (Circuit.qap_sparse)."""
+        self.run(d_inputs_ptr, count, d_out_ptr)
+        return self.ctx.qap_check_dev(qap, d_out_ptr, self.m, count)
+
     def run_numpy(self, inputs):
         """inputs (count, n_in, 4) uint64 -> (count, m, 4) uint64, staged through torch tensors on the context's device."""
         import torch

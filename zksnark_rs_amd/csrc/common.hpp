@@ -107,6 +107,7 @@ struct NttTables;  // ntt.hip
 struct MsmWorkspace;  // kernels.hpp
 struct ProveState;    // prove.hip
 struct VerifyBatchState;   // verify_batch.hip
+struct QapCheckState;      // qap_check.hip
 
 }  // namespace zk
 
@@ -118,6 +119,7 @@ struct zk_ctx {
     hipStream_t main_alt = nullptr;  // second main stream: odd-numbered proof slots run their SpMV / NTT stage here
     std::shared_ptr<zk::ProveState> prove_state;
     std::shared_ptr<zk::VerifyBatchState> verify_batch;   // zk_verify_batch: its stream and buffers
+    std::shared_ptr<zk::QapCheckState> qap_check;         // zk_qap_check*: its stream and buffers
     hipEvent_t submit_wait_evt = nullptr;   // consumed by the next prove_submit / prove_msm_submit: its first kernels wait for this event (comm.hip)
     int cur_slot = -1;
     std::string last_error;
@@ -137,6 +139,8 @@ struct zk_ctx {
     long opt_tail_stream = 0;     // merged L + H product: its reduction tail on the idle L stream (measurement switch)
     long opt_ntt_fuse = 1;        // roots-of-unity form, two-pass sizes: element-wise kernels folded into the DIF tile loads / stores (ntt_dif_fused); measurement switch
     long opt_witgen_scratch_kib = 8L << 20;   // zk_witgen_create: cap of the slot scratch a generator keeps in HBM, KiB (8 GiB); groups of 64 instances run in chunks under it
+    long opt_qap_check_chunk = (long)ZK_QAP_CHECK_CHUNK_LANES;   // zk_qap_check*: (instance, gate) pairs per launch (qap_check.hip)
+    long opt_qap_check_by_instance = 0;   // zk_qap_check*: 1 = consecutive lanes take the same gate of consecutive instances (the A/B of DESIGN 4h)
     long opt_merge_lh = 1;        // prove: L (witness over sum_delta) and H + r B1 + s A as ONE inner product over the table xi_t | xi | sum_delta (one bucket set, one tail); 0 = two products
     long opt_chain_order = 1;     // order of the accumulation chain of a proof: 0 = (L,) B2, A, HB; 1 = (L,) A, B2, HB; 2 = B2, (L,) HB, A.  Round 5, L merged into HB: 1 = 102.2 against 101.2 (0) and 100.8 (2) proofs/s, profiles/r5_experiments.txt item 5
     long opt_fold = 4;            // images summed per lane and pass in the row / column sums of the MSM tail

@@ -40,6 +40,9 @@ struct zk_qap {
     // sparse form (roots w^j): by gate (prove: evaluation vectors) and by wire (setup: u_i(x))
     zk::DevCsr u_gate, v_gate;
     zk::DevCsr u_wire, v_wire, w_wire;
+    // W by gate, values times R like u_gate / v_gate: built by the first zk_qap_check* of the handle (qap_check.hip), never by the prover
+    mutable zk::DevCsr w_gate;
+    mutable bool has_w_gate = false;
     // dense form: m x n coefficient matrices and t (n+1), Montgomery (arbitrary-roots form: t only)
     zk::DevBuf<zk::Fr> du, dv, dw, dt;
     size_t t_degree = 0;      // actual degree of t (dense)

@@ -74,6 +74,18 @@ def prove(qap, sigma, weights, rs=None):
     return qap.ctx.prove(sigmag1.crs, qap.handle, weights, r, s)
 
 
+def is_satisfied(qap, weights):
+    """Would prove(qap, sigma, weights) yield a proof that verifies?  True iff every gate holds (U_j V_j == W_j) and weights[0] == 1,
+    decided on the GPU before anything is proved (zk_qap_check; sparse QAP forms: QAP.from_zk(..., sparse=True))."""
+    bad, _, wire0_ok = qap.ctx.qap_check(qap.handle, weights)
+    return bad == 0 and wire0_ok
+
+
+def first_unsatisfied(qap, weights):
+    """The lowest gate (0-based row of the root representation) with U_j V_j != W_j, None when every gate holds."""
+    return qap.ctx.qap_check(qap.handle, weights)[1]
+
+
 def verify(sigma, inputs, proof):
     sigmag1, sigmag2 = sigma
     return sigmag1.ctx.verify(sigmag1.crs, inputs, proof)
