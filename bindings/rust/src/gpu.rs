@@ -74,6 +74,13 @@ extern "C" {
                        ok: *mut c_int) -> c_int;
     fn zk_verify_batch_all(ctx: *mut ZkCtx, crs: *const ZkCrs, inputs: *const u64, n_inputs: usize, proofs: *const u8, n_proofs: usize,
                            z: *const u64, ok: *mut c_int) -> c_int;
+    fn zk_verify_batch_compressed(ctx: *mut ZkCtx, crs: *const ZkCrs, inputs: *const u64, n_inputs: usize, proofs: *const u8, n_proofs: usize,
+                                  ok: *mut c_int) -> c_int;
+    // the 259-byte proof <-> the compressed 128-byte form: on the host (no context), or for n proofs on the GPU
+    fn zk_proof_compress(proof: *const u8, out: *mut u8) -> c_int;
+    fn zk_proof_decompress(input: *const u8, proof_out: *mut u8) -> c_int;
+    fn zk_proof_compress_batch(ctx: *mut ZkCtx, proofs: *const u8, n: usize, out: *mut u8, ok: *mut c_int) -> c_int;
+    fn zk_proof_decompress_batch(ctx: *mut ZkCtx, input: *const u8, n: usize, proofs_out: *mut u8, ok: *mut c_int) -> c_int;
     // the .zk front end's witness as a compiled tape: one witness on the host, or a whole batch on the GPU with the witnesses left in
     // HBM where zk_prove_batch_submit takes them (d_weights_out + j * m * 32 bytes is witness j)
     fn zk_circuit_parse(code: *const c_char, out: *mut *mut ZkCircuit, err: *mut c_char, err_len: usize) -> c_int;
@@ -347,6 +354,23 @@ fn proof_to_bytes(p: &Proof<G1Local, G2Local>) -> [u8; 259] {
     b
 }
 
+/// The compressed form of a proof (zkgpu.h "Compressed proof bytes"): A 32 | B 64 | C 32 bytes, x coordinates big-endian with
+/// the sign of y (taken on the canonical integer) in the two top bits of each block.  Host code: no device is involved.
+impl Proof<G1Local, G2Local> {
+    pub fn to_compressed(&self) -> [u8; 128] {
+        let (bytes, mut out) = (proof_to_bytes(self), [0u8; 128]);
+        let st = unsafe { zk_proof_compress(bytes.as_ptr(), out.as_mut_ptr()) };
+        assert!(st == 0, "zk_proof_compress: status {}", st);   // bn's points are on their curves: cannot fail for a Proof
+        out
+    }
+    /// None unless all three blocks are valid encodings of points on their curves.  B's subgroup is not tested here: verify does.
+    pub fn from_compressed(c: &[u8; 128]) -> Option<Self> {
+        let mut bytes = [0u8; 259];
+        let st = unsafe { zk_proof_decompress(c.as_ptr(), bytes.as_mut_ptr()) };
+        if st == 0 { Some(proof_from_bytes(&bytes)) } else { None }
+    }
+}
+
 fn g1s(ps: &[G1Local]) -> Vec<u64> { ps.iter().flat_map(|p| g1_to_words(p).to_vec()).collect() }
 fn g2s(ps: &[G2Local]) -> Vec<u64> { ps.iter().flat_map(|p| g2_to_words(p).to_vec()).collect() }
 fn frs(xs: &[FrLocal]) -> Vec<u64> { xs.iter().flat_map(|x| fr_to_words(x).to_vec()).collect() }
@@ -589,6 +613,18 @@ impl GpuProver {
         let bytes: Vec<u8> = proofs.iter().flat_map(|p| proof_to_bytes(p).to_vec()).collect();
         let mut ok = vec![0 as c_int; proofs.len()];
         unsafe { check(self.ctx.0, zk_verify_batch(self.ctx.0, self.crs, x.as_ptr(), k, bytes.as_ptr(), proofs.len(), ok.as_mut_ptr())); }
+        ok.into_iter().map(|v| v == 1).collect()
+    }
+    /// verify_batch over compressed proofs (Proof::to_compressed), decompressed on the GPU (zk_verify_batch_compressed): entry j is
+    /// true iff proofs[j] decompresses and verify accepts the result
+    pub fn verify_batch_compressed(&self, inputs: &[Vec<FrLocal>], proofs: &[[u8; 128]]) -> Vec<bool> {
+        assert!(inputs.len() == proofs.len(), "one input row per proof");
+        let k = inputs.first().map_or(0, |r| r.len());
+        assert!(inputs.iter().all(|r| r.len() == k), "every proof needs the same number of inputs");
+        let x: Vec<u64> = inputs.iter().flat_map(|r| frs(r)).collect();
+        let bytes: Vec<u8> = proofs.iter().flat_map(|p| p.to_vec()).collect();
+        let mut ok = vec![0 as c_int; proofs.len()];
+        unsafe { check(self.ctx.0, zk_verify_batch_compressed(self.ctx.0, self.crs, x.as_ptr(), k, bytes.as_ptr(), proofs.len(), ok.as_mut_ptr())); }
         ok.into_iter().map(|v| v == 1).collect()
     }
     /// one verdict for many proofs on the GPU (zk_verify_batch_all): true iff every proof decodes and the random linear

@@ -19,6 +19,21 @@
  *       G1: 0x04 | x | y                          (32-byte big-endian each)
  *       G2: 0x04 | x.c1 | x.c0 | y.c1 | y.c0      (EIP-197 order)
  *       infinity: 0x00 followed by zero bytes (same total length).
+ *   - Compressed proof bytes (zk_proof_compress and the calls next to it): 128 bytes
+ *       A (G1, 32 B) | B (G2, 64 B) | C (G1, 32 B)
+ *       G1: x, 32-byte big-endian.  G2: x.c1 | x.c0, 32-byte big-endian each (EIP-197 order, as above).
+ *       q < 2^254, so the two top bits of a coordinate's first byte are free; bits 7..6 of a block's byte 0 hold a flag:
+ *         10  finite point; y is the SMALLER of {y, q - y}
+ *         11  finite point; y is the LARGER
+ *         01  infinity; every other bit of the block must be 0
+ *         00  never valid (all-zero blocks included)
+ *       x = the value with the flag bits cleared and must be < q (G2: both halves; the two top bits of byte 32, x.c0's first
+ *       byte, must be 0).  "Larger" is decided on the CANONICAL INTEGER y in [0, q), never on a Montgomery residue:
+ *       y > (q - 1) / 2; for G2: if y.c1 != 0 then y.c1 > (q - 1) / 2, else y.c0 > (q - 1) / 2.
+ *       One byte string per point: x in range and x^3 + 3 (x^3 + b' on the twist) a square.  y = 0 cannot occur (both curve
+ *       orders are odd: r, and r (2q - r), so there is no 2-torsion); were it ever met, only flag 10 would be accepted.
+ *       Decompression checks encoding and curve membership only, NOT the order-r subgroup of B: that test stays behind every
+ *       verify call, which rejects a twist point outside G2 whichever form carried it.
  *   - A zk_ctx is bound to one HIP device and must be used from one thread at a time.
  *   - All `const uint64_t*` inputs are HOST pointers unless the parameter name starts with d_.
  */
@@ -49,6 +64,7 @@ typedef enum {
 } zk_status;
 
 #define ZK_PROOF_BYTES 259
+#define ZK_PROOF_COMPRESSED_BYTES 128
 #define ZK_MAX_IN_FLIGHT 4   /* proofs one context can have submitted and not yet waited for */
 #define ZK_FR_WORDS 4
 #define ZK_G1_WORDS 8
@@ -328,6 +344,24 @@ int zk_qap_save(zk_ctx* ctx, const zk_qap* qap, const char* path);
 int zk_qap_load(zk_ctx* ctx, const char* path, zk_qap** out);
 int zk_proof_save(const uint8_t proof[ZK_PROOF_BYTES], const char* path);
 int zk_proof_load(const char* path, uint8_t proof_out[ZK_PROOF_BYTES]);
+/* The 259-byte proof <-> the compressed 128-byte form ("Compressed proof bytes" above; Proof has no encoding in the reference,
+ * mod.rs:124-128).  Host code, no context (as zk_pairing / zk_proof_save).
+ * zk_proof_compress: ZK_OK iff every block of `proof` has a legal tag (0x00 followed by zeros, or 0x04), coordinates < q and
+ * lies on its curve; it does not run the subgroup test of B.  Otherwise ZK_ERR_RANGE and `out` = 128 zero bytes (flag 00, which
+ * no decoder accepts).  zk_proof_decompress: ZK_OK iff all three blocks are valid encodings; otherwise ZK_ERR_RANGE and
+ * `proof_out` = 259 bytes of 0xFF (tag 0xFF is refused by every decoder; 259 zero bytes would be a VALID proof of three
+ * infinities).  decompress(compress(p)) == p for every p that compresses and compress(decompress(c)) == c for every c that
+ * decompresses.  A null pointer: ZK_ERR_ARG, nothing written. */
+int zk_proof_compress(const uint8_t proof[ZK_PROOF_BYTES], uint8_t out[ZK_PROOF_COMPRESSED_BYTES]);
+int zk_proof_decompress(const uint8_t in[ZK_PROOF_COMPRESSED_BYTES], uint8_t proof_out[ZK_PROOF_BYTES]);
+/* The same for n proofs in host memory on the GPU, one lane per point: entry j of the output and ok[j] are what the single form
+ * writes and whether it returns ZK_OK, for every j < n (an invalid entry: ok[j] = 0 and the 0xFF / zero fill above).  The return
+ * value is ZK_OK unless the call itself fails.  n == 0: ZK_OK, nothing touched.  Null ctx / input / output / ok: ZK_ERR_ARG.  Any n:
+ * the proofs go through the device ZK_VERIFY_BATCH_CHUNK at a time and the results do not depend on the chunking.  Synchronous, on
+ * zk_verify_batch's stream: no device-wide synchronisation, an outstanding zk_prove_submit ticket is neither waited for nor
+ * disturbed. */
+int zk_proof_compress_batch(zk_ctx* ctx, const uint8_t* proofs, size_t n, uint8_t* out, int* ok);
+int zk_proof_decompress_batch(zk_ctx* ctx, const uint8_t* in, size_t n, uint8_t* proofs_out, int* ok);
 
 /* ------------------------------------------------------------------------------------------
  * prove  (groth16::prove, groth16/mod.rs:213-296) with (r, s) injected (mod.rs:231)
@@ -518,6 +552,12 @@ int zk_verify(zk_ctx* ctx, const zk_crs* crs, const uint64_t* inputs, size_t n_i
  * disturbed. */
 #define ZK_VERIFY_BATCH_CHUNK 65536
 int zk_verify_batch(zk_ctx* ctx, const zk_crs* crs, const uint64_t* inputs, size_t n_inputs, const uint8_t* proofs, size_t n_proofs, int* ok);
+/* zk_verify_batch over compressed proofs: proofs = n_proofs x ZK_PROOF_COMPRESSED_BYTES bytes, decompressed on the GPU in front
+ * of the same kernels; ok[j] = 1 iff entry j decompresses (zk_proof_decompress) AND zk_verify accepts the result.  Arguments,
+ * statuses, chunking and stream are exactly zk_verify_batch's.  Not offered: a compressed form of zk_verify_batch_all (call
+ * zk_proof_decompress_batch first), a compressed ZKPRFv1 file, compressed CRS points. */
+int zk_verify_batch_compressed(zk_ctx* ctx, const zk_crs* crs, const uint64_t* inputs, size_t n_inputs, const uint8_t* proofs,
+                               size_t n_proofs, int* ok);
 /* One verdict for a whole batch on the GPU, by a random linear combination: *ok = 1 iff every proof passes zk_verify's
  * decoder (tag rules, coordinates < q, on the curve, [r]B = infinity) and
  *     prod_j e(A_j, B_j)^{z_j} = e(alpha, beta)^{t_0} e(T_S, gamma) e(T_C, delta),

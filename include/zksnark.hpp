@@ -258,6 +258,26 @@ struct Proof {
     bool operator==(const Proof& o) const { return bytes == o.bytes; }
 };
 
+// the same proof in the compressed 128-byte form (zkgpu.h "Compressed proof bytes": x coordinates, the sign of y in a flag)
+struct CompressedProof {
+    std::array<uint8_t, ZK_PROOF_COMPRESSED_BYTES> bytes{};
+    bool operator==(const CompressedProof& o) const { return bytes == o.bytes; }
+};
+// zk_proof_compress / zk_proof_decompress: host code, no context.  Error(ZK_ERR_RANGE) for a proof that is no canonical encoding
+// of points on their curves / for bytes that are no valid compressed proof.
+inline CompressedProof compress(const Proof& p) {
+    CompressedProof c;
+    const int st = zk_proof_compress(p.bytes.data(), c.bytes.data());
+    if (st != ZK_OK) throw Error(st, "groth16::compress: not a canonical proof encoding");
+    return c;
+}
+inline Proof decompress(const CompressedProof& c) {
+    Proof p;
+    const int st = zk_proof_decompress(c.bytes.data(), p.bytes.data());
+    if (st != ZK_OK) throw Error(st, "groth16::decompress: not a valid compressed proof");
+    return p;
+}
+
 // weights(code, assignments) (circuit/mod.rs:529-637)
 inline std::vector<FrLocal> weights(const std::string& code, const std::vector<FrLocal>& assignments) {
     return ASTParser::try_parse(code).weights(assignments);
@@ -331,6 +351,25 @@ inline std::vector<bool> verify_batch(const Context& c, const Sigma& sigma, cons
     }
     std::vector<int> ok(n, 0);
     c.check(zk_verify_batch(c.get(), sigma.get(), k ? x.data() : nullptr, k, bytes.data(), n, ok.data()), "groth16::verify_batch");
+    return std::vector<bool>(ok.begin(), ok.end());
+}
+
+// verify_batch over compressed proofs, decompressed on the GPU (zk_verify_batch_compressed): entry j is true iff proofs[j]
+// decompresses and verify accepts the result
+inline std::vector<bool> verify_batch_compressed(const Context& c, const Sigma& sigma, const std::vector<std::vector<FrLocal>>& inputs,
+                                                 const std::vector<CompressedProof>& proofs) {
+    if (inputs.size() != proofs.size()) throw Error(ZK_ERR_ARG, "groth16::verify_batch_compressed: one input row per proof");
+    const size_t n = proofs.size(), k = n ? inputs[0].size() : 0;
+    std::vector<uint64_t> x(n * k * 4);
+    std::vector<uint8_t> bytes(n * ZK_PROOF_COMPRESSED_BYTES);
+    for (size_t j = 0; j < n; ++j) {
+        if (inputs[j].size() != k) throw Error(ZK_ERR_ARG, "groth16::verify_batch_compressed: every proof needs the same number of inputs");
+        for (size_t i = 0; i < k; ++i) std::copy(inputs[j][i].w.begin(), inputs[j][i].w.end(), x.begin() + (j * k + i) * 4);
+        std::copy(proofs[j].bytes.begin(), proofs[j].bytes.end(), bytes.begin() + j * ZK_PROOF_COMPRESSED_BYTES);
+    }
+    std::vector<int> ok(n, 0);
+    c.check(zk_verify_batch_compressed(c.get(), sigma.get(), k ? x.data() : nullptr, k, bytes.data(), n, ok.data()),
+            "groth16::verify_batch_compressed");
     return std::vector<bool>(ok.begin(), ok.end());
 }
 

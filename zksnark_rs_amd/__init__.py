@@ -18,13 +18,14 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import PROOF_BYTES, PARTIAL_BYTES, MAX_IN_FLIGHT, MAX_BATCH
+from ._lib import PROOF_BYTES, PROOF_COMPRESSED_BYTES, PARTIAL_BYTES, MAX_IN_FLIGHT, MAX_BATCH
 
 R_MODULUS = 21888242871839275222246405745257275088548364400416034343698204186575808495617
 Q_MODULUS = 21888242871839275222246405745257275088696311157297823662689037894645226208583
 
 __all__ = ["Context", "ZkError", "fr_to_limbs", "limbs_to_int", "ints_to_limbs", "limbs_to_ints",
-           "PROOF_BYTES", "PARTIAL_BYTES", "MAX_IN_FLIGHT", "MAX_BATCH", "R_MODULUS", "Q_MODULUS", "SplitMix64", "pairing", "proof_save", "proof_load"]
+           "PROOF_BYTES", "PARTIAL_BYTES", "MAX_IN_FLIGHT", "MAX_BATCH", "R_MODULUS", "Q_MODULUS", "SplitMix64", "pairing", "proof_save", "proof_load",
+           "PROOF_COMPRESSED_BYTES", "proof_compress", "proof_decompress"]
 
 
 class ZkError(RuntimeError):
@@ -117,6 +118,32 @@ def proof_load(path):
     if rc != 0:
         raise ZkError(rc)
     return bytes(buf)
+
+
+def proof_compress(proof):
+    """zk_proof_compress (host code): the 259-byte proof -> its 128-byte compressed form.  ZkError(ZK_ERR_RANGE) unless every
+    block has a legal tag, coordinates < q and lies on its curve (the subgroup of B is not tested here)."""
+    if len(proof) != PROOF_BYTES:
+        raise ValueError("proof_compress: a proof is %d bytes" % PROOF_BYTES)
+    src = (C.c_uint8 * PROOF_BYTES).from_buffer_copy(bytes(proof))
+    dst = (C.c_uint8 * PROOF_COMPRESSED_BYTES)()
+    rc = _lib.load().zk_proof_compress(src, dst)
+    if rc != 0:
+        raise ZkError(rc, "proof_compress: not a canonical proof encoding")
+    return bytes(dst)
+
+
+def proof_decompress(compressed):
+    """zk_proof_decompress (host code): 128 bytes -> the 259-byte proof.  ZkError(ZK_ERR_RANGE) unless all three blocks are
+    valid encodings of points on their curves."""
+    if len(compressed) != PROOF_COMPRESSED_BYTES:
+        raise ValueError("proof_decompress: a compressed proof is %d bytes" % PROOF_COMPRESSED_BYTES)
+    src = (C.c_uint8 * PROOF_COMPRESSED_BYTES).from_buffer_copy(bytes(compressed))
+    dst = (C.c_uint8 * PROOF_BYTES)()
+    rc = _lib.load().zk_proof_decompress(src, dst)
+    if rc != 0:
+        raise ZkError(rc, "proof_decompress: not a valid compressed proof")
+    return bytes(dst)
 
 
 class _Handle:
@@ -535,12 +562,12 @@ class Context:
         return bool(ok.value)
 
     @staticmethod
-    def _batch_args(inputs, proofs, name):
-        """(inputs as (N, k, 4) uint64, proofs as (N, 259) uint8) for the batch verify calls"""
+    def _batch_args(inputs, proofs, name, proof_bytes=PROOF_BYTES):
+        """(inputs as (N, k, 4) uint64, proofs as (N, proof_bytes) uint8) for the batch verify calls"""
         if isinstance(proofs, np.ndarray):
-            pb = np.ascontiguousarray(proofs, dtype=np.uint8).reshape(-1, PROOF_BYTES)
+            pb = np.ascontiguousarray(proofs, dtype=np.uint8).reshape(-1, proof_bytes)
         else:
-            pb = np.frombuffer(b"".join(bytes(p) for p in proofs), dtype=np.uint8).reshape(-1, PROOF_BYTES).copy()
+            pb = np.frombuffer(b"".join(bytes(p) for p in proofs), dtype=np.uint8).reshape(-1, proof_bytes).copy()
         n = pb.shape[0]
         if isinstance(inputs, np.ndarray) and inputs.ndim == 3:
             a = np.ascontiguousarray(inputs, dtype=np.uint64)
@@ -564,6 +591,49 @@ class Context:
         self._check(self.lib.zk_verify_batch(self.ptr, crs.ptr, a.ctypes.data_as(_lib.u64p) if a.size else None, a.shape[1],
                                              pb.ctypes.data_as(_lib.u8p), n, ok.ctypes.data_as(C.POINTER(C.c_int))))
         return ok.astype(bool)
+
+    @staticmethod
+    def _proof_rows(proofs, width, name):
+        """a list of byte strings or an (N, width) uint8 array -> a contiguous (N, width) uint8 array"""
+        if isinstance(proofs, np.ndarray):
+            a = np.ascontiguousarray(proofs, dtype=np.uint8)
+            return a.reshape(a.size // width, width)
+        rows = [bytes(p) for p in proofs]
+        if any(len(r) != width for r in rows):
+            raise ValueError("%s: every entry is %d bytes" % (name, width))
+        return np.frombuffer(b"".join(rows), dtype=np.uint8).reshape(len(rows), width).copy()
+
+    def verify_batch_compressed(self, crs, inputs, proofs):
+        """zk_verify_batch_compressed: verify_batch over 128-byte proofs (a list of strings or an (N, 128) uint8 array), decompressed
+        on the GPU -> (N,) bool array, entry j true iff proofs[j] decompresses and verify accepts the result."""
+        a, pb = self._batch_args(inputs, proofs, "verify_batch_compressed", PROOF_COMPRESSED_BYTES)
+        n = pb.shape[0]
+        ok = np.zeros(n, dtype=np.int32)
+        self._check(self.lib.zk_verify_batch_compressed(self.ptr, crs.ptr, a.ctypes.data_as(_lib.u64p) if a.size else None, a.shape[1],
+                                                        pb.ctypes.data_as(_lib.u8p), n, ok.ctypes.data_as(C.POINTER(C.c_int))))
+        return ok.astype(bool)
+
+    # ---- the compressed proof form ----
+    proof_compress = staticmethod(proof_compress)        # host code, no device work: the module functions
+    proof_decompress = staticmethod(proof_decompress)
+
+    def _codec_batch(self, fn, entries, width_in, width_out, name):
+        src = self._proof_rows(entries, width_in, name)
+        n = src.shape[0]
+        out = np.zeros((n, width_out), dtype=np.uint8)
+        ok = np.zeros(n, dtype=np.int32)
+        self._check(fn(self.ptr, src.ctypes.data_as(_lib.u8p), n, out.ctypes.data_as(_lib.u8p), ok.ctypes.data_as(C.POINTER(C.c_int))))
+        return out, ok.astype(bool)
+
+    def proof_compress_batch(self, proofs):
+        """zk_proof_compress_batch on the GPU: N 259-byte proofs -> ((N, 128) uint8 array, (N,) bool array); an entry that is no
+        canonical proof encoding gives ok = False and 128 zero bytes."""
+        return self._codec_batch(self.lib.zk_proof_compress_batch, proofs, PROOF_BYTES, PROOF_COMPRESSED_BYTES, "proof_compress_batch")
+
+    def proof_decompress_batch(self, compressed):
+        """zk_proof_decompress_batch on the GPU: N 128-byte strings -> ((N, 259) uint8 array, (N,) bool array); an entry that is no
+        valid encoding gives ok = False and 259 bytes of 0xFF."""
+        return self._codec_batch(self.lib.zk_proof_decompress_batch, compressed, PROOF_COMPRESSED_BYTES, PROOF_BYTES, "proof_decompress_batch")
 
     def verify_batch_all(self, crs, inputs, proofs, z=None):
         """zk_verify_batch_all: one verdict for the whole batch -> True iff every proof decodes and the random linear combination

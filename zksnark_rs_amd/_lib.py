@@ -14,6 +14,7 @@ ZK_ERR_ARG, ZK_ERR_HIP, ZK_ERR_NO_DEVICE, ZK_ERR_SIZE, ZK_ERR_DIV_BY_ZERO, ZK_ER
 ZK_ERR_IO, ZK_ERR_COMM = -8, -9
 COMM_ID_BYTES = 128
 PROOF_BYTES = 259
+PROOF_COMPRESSED_BYTES = 128   # ZK_PROOF_COMPRESSED_BYTES
 PARTIAL_BYTES = 768
 MAX_IN_FLIGHT = 4      # ZK_MAX_IN_FLIGHT
 MAX_BATCH = 64          # ZK_MAX_BATCH
@@ -154,6 +155,10 @@ SIGNATURES = {
     "zk_qap_load": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_void_p)]),
     "zk_proof_save": (C.c_int, [u8p, C.c_char_p]),
     "zk_proof_load": (C.c_int, [C.c_char_p, u8p]),
+    "zk_proof_compress": (C.c_int, [u8p, u8p]),
+    "zk_proof_decompress": (C.c_int, [u8p, u8p]),
+    "zk_proof_compress_batch": (C.c_int, [C.c_void_p, u8p, C.c_size_t, u8p, C.POINTER(C.c_int)]),
+    "zk_proof_decompress_batch": (C.c_int, [C.c_void_p, u8p, C.c_size_t, u8p, C.POINTER(C.c_int)]),
     "zk_device_count": (C.c_int, []),
     "zk_comm_unique_id": (C.c_int, [u8p]),
     "zk_comm_init": (C.c_int, [C.c_void_p, u8p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
@@ -178,6 +183,7 @@ SIGNATURES = {
     "zk_mgpu_last_error": (C.c_char_p, [C.c_void_p]),
     "zk_verify": (C.c_int, [C.c_void_p, C.c_void_p, u64p, C.c_size_t, u8p, C.POINTER(C.c_int)]),
     "zk_verify_batch": (C.c_int, [C.c_void_p, C.c_void_p, u64p, C.c_size_t, u8p, C.c_size_t, C.POINTER(C.c_int)]),
+    "zk_verify_batch_compressed": (C.c_int, [C.c_void_p, C.c_void_p, u64p, C.c_size_t, u8p, C.c_size_t, C.POINTER(C.c_int)]),
     "zk_verify_batch_all": (C.c_int, [C.c_void_p, C.c_void_p, u64p, C.c_size_t, u8p, C.c_size_t, u64p, C.POINTER(C.c_int)]),
     "zk_pairing": (C.c_int, [u64p, u64p, u64p]),
     "zk_profile_reset": (C.c_int, [C.c_void_p]),

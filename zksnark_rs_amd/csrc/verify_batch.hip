@@ -9,6 +9,8 @@
 //   k_vb_final    ok_j = decoded_j && final_exp_exact(f_j) == 1
 // The host checks the inputs' range and the CRS points exactly as zk_verify does, computes c and the fixed lines, uploads bytes
 // and inputs and reads the verdicts back.  Everything runs on the call's own stream.
+// zk_verify_batch_compressed is the same call over 128-byte proofs: a chunk is decompressed on the device (proof_codec.hip) into
+// the 259-byte strings k_vb_decode reads; a string that does not decompress arrives there as 0xFF bytes and is refused by tag.
 #define ZK_MUL_OUTLINE 1
 #include "pipeline.hpp"
 #include "pairing.cuh"
@@ -97,8 +99,11 @@ __global__ void __launch_bounds__(VB_BLOCK) k_vb_final(const Fq12* F, const int*
 
 using namespace zk;
 
-extern "C" int zk_verify_batch(zk_ctx* ctx, const zk_crs* crs, const uint64_t* inputs, size_t n_inputs, const uint8_t* proofs,
-                               size_t n_proofs, int* ok) {
+// the body of zk_verify_batch and zk_verify_batch_compressed: `proofs` holds n_proofs strings of 259 bytes, or of 128 when
+// `compressed`; a chunk of the latter is uploaded as it is and decompressed into d_proofs on the device.  The error rules of the
+// compressed call are zk_verify_batch's exactly, texts included: its zk_last_error also reads "verify_batch: ...", on purpose.
+static int verify_batch_impl(zk_ctx* ctx, const zk_crs* crs, const uint64_t* inputs, size_t n_inputs, const uint8_t* proofs,
+                             size_t n_proofs, int* ok, bool compressed) {
     if (!ctx || !crs) return ZK_ERR_ARG;
     if (n_proofs == 0) return ZK_OK;
     if (!proofs || !ok || (n_inputs && !inputs)) return ZK_ERR_ARG;
@@ -148,7 +153,9 @@ extern "C" int zk_verify_batch(zk_ctx* ctx, const zk_crs* crs, const uint64_t* i
         const size_t o_lines = 0, o_c = o_lines + up(h_lines.size() * sizeof(Line)), o_proofs = o_c + up(sizeof(Fq12));
         const size_t o_x = o_proofs + up(m_max * ZK_PROOF_BYTES), o_A = o_x + up(m_max * k * 32), o_B = o_A + up(m_max * sizeof(G1A));
         const size_t o_C = o_B + up(m_max * sizeof(G2A)), o_S = o_C + up(m_max * sizeof(G1A)), o_F = o_S + up(m_max * sizeof(G1A));
-        const size_t o_dec = o_F + up(m_max * sizeof(Fq12)), o_ok = o_dec + up(m_max * sizeof(int)), total = o_ok + up(m_max * sizeof(int));
+        const size_t o_dec = o_F + up(m_max * sizeof(Fq12)), o_ok = o_dec + up(m_max * sizeof(int));
+        // the 128-byte strings of a chunk, behind everything zk_verify_batch itself lays out
+        const size_t o_cin = o_ok + up(m_max * sizeof(int)), total = o_cin + (compressed ? up(m_max * ZK_PROOF_COMPRESSED_BYTES) : 0);
         if (st.arena.n < total) {
             if (st.arena.p) st.retired.push_back(std::move(st.arena));
             st.arena.alloc(total);
@@ -169,7 +176,13 @@ extern "C" int zk_verify_batch(zk_ctx* ctx, const zk_crs* crs, const uint64_t* i
         for (size_t j0 = 0; j0 < n_proofs; j0 += m_max) {
             const size_t m = std::min(m_max, n_proofs - j0);
             const unsigned grid = ceil_div(m, VB_BLOCK);
-            ZK_HIP(hipMemcpyAsync(d_proofs, proofs + j0 * ZK_PROOF_BYTES, m * ZK_PROOF_BYTES, hipMemcpyHostToDevice, s));
+            if (compressed) {
+                uint8_t* d_cin = base + o_cin;
+                ZK_HIP(hipMemcpyAsync(d_cin, proofs + j0 * ZK_PROOF_COMPRESSED_BYTES, m * ZK_PROOF_COMPRESSED_BYTES, hipMemcpyHostToDevice, s));
+                pc_launch_decompress(d_cin, m, d_proofs, s);
+            } else {
+                ZK_HIP(hipMemcpyAsync(d_proofs, proofs + j0 * ZK_PROOF_BYTES, m * ZK_PROOF_BYTES, hipMemcpyHostToDevice, s));
+            }
             if (k) {
                 const uint64_t* src = inputs + j0 * n_inputs * 4;
                 if (k != n_inputs) {   // only the first k inputs of a row are read (zip truncation)
@@ -191,4 +204,13 @@ extern "C" int zk_verify_batch(zk_ctx* ctx, const zk_crs* crs, const uint64_t* i
             ZK_HIP(hipStreamSynchronize(s));   // also keeps `packed` and the arena's chunk arrays free for the next chunk
         }
     });
+}
+
+extern "C" int zk_verify_batch(zk_ctx* ctx, const zk_crs* crs, const uint64_t* inputs, size_t n_inputs, const uint8_t* proofs,
+                               size_t n_proofs, int* ok) {
+    return verify_batch_impl(ctx, crs, inputs, n_inputs, proofs, n_proofs, ok, false);
+}
+extern "C" int zk_verify_batch_compressed(zk_ctx* ctx, const zk_crs* crs, const uint64_t* inputs, size_t n_inputs, const uint8_t* proofs,
+                                          size_t n_proofs, int* ok) {
+    return verify_batch_impl(ctx, crs, inputs, n_inputs, proofs, n_proofs, ok, true);
 }

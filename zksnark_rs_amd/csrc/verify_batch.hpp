@@ -1,5 +1,6 @@
-// verify_batch.hpp -- what zk_verify_batch (verify_batch.hip) and zk_verify_batch_all (verify_batch_all.hip) share: the call's
-// stream and grow-only arena kept by the context, and the re-check of the CRS points through zk_verify's readers.
+// verify_batch.hpp -- what zk_verify_batch (verify_batch.hip), zk_verify_batch_all (verify_batch_all.hip) and the batch forms of
+// the proof codec (proof_codec.hip) share: the call's stream and grow-only arena kept by the context, and the re-check of the
+// CRS points through zk_verify's readers.
 #pragma once
 #include "common.hpp"
 #include "pairing.cuh"
@@ -16,6 +17,10 @@ struct VerifyBatchState {
         if (stream) (void)hipStreamDestroy(stream);
     }
 };
+
+// proof_codec.hip: d_proofs[259 j ..) = the 259-byte form of d_in[128 j ..) for j < m, by the two decompress kernels on stream s.
+// A block that is no valid encoding comes out as 0xFF bytes, which no decoder of the 259-byte form accepts.
+void pc_launch_decompress(const uint8_t* d_in, size_t m, uint8_t* d_proofs, hipStream_t s);
 
 static inline void words_of(const Fq& x, uint64_t* w) {
     const Fq c = x.to_canonical();

@@ -10,6 +10,7 @@
 import os
 
 from . import R_MODULUS, ints_to_limbs
+from . import proof_compress as _proof_compress, proof_decompress as _proof_decompress
 from .circuit import Circuit
 
 
@@ -95,6 +96,22 @@ def verify_batch(sigma, inputs, proofs):
     """verify for many proofs over one CRS on the GPU: inputs[j] (the same count for every j) against proofs[j] -> bool array"""
     sigmag1, sigmag2 = sigma
     return sigmag1.ctx.verify_batch(sigmag1.crs, inputs, proofs)
+
+
+def verify_batch_compressed(sigma, inputs, proofs):
+    """verify_batch over compressed 128-byte proofs (compress), decompressed on the GPU -> bool array"""
+    sigmag1, sigmag2 = sigma
+    return sigmag1.ctx.verify_batch_compressed(sigmag1.crs, inputs, proofs)
+
+
+def compress(proof):
+    """the 259-byte proof -> the usual 128-byte form: x coordinates with the sign of y in a flag (include/zkgpu.h)"""
+    return _proof_compress(proof)
+
+
+def decompress(compressed):
+    """128 bytes -> the 259-byte proof verify takes; raises unless every point decodes onto its curve"""
+    return _proof_decompress(compressed)
 
 
 def verify_batch_all(sigma, inputs, proofs):
