@@ -50,6 +50,14 @@ pub struct ZkSparseRows { ptr: *const u64, gate: *const u32, val: *const u64 }  
 pub struct ZkQapSparseDesc { log_n: c_uint, m: usize, input: usize, u: ZkSparseRows, v: ZkSparseRows, w: ZkSparseRows }
 #[repr(C)]
 pub struct ZkQapCheckResult { pub bad_gates: u32, pub first_bad: u32, pub flags: u32 }   // zk_qap_check_result (12 bytes)
+#[repr(C)] pub struct ZkVk { _p: [u8; 0] }
+#[repr(C)]
+pub struct ZkVkDesc {                                    // zk_vk_desc
+    input: usize,
+    alpha_g1: *const u64,
+    beta_g2: *const u64, gamma_g2: *const u64, delta_g2: *const u64,
+    sum_gamma_g1: *const u64,
+}
 pub const ZK_QAP_CHECK_NONE: u32 = 0xFFFF_FFFF;
 pub const ZK_QAP_CHECK_WIRE0: u32 = 1;
 
@@ -76,6 +84,24 @@ extern "C" {
                            z: *const u64, ok: *mut c_int) -> c_int;
     fn zk_verify_batch_compressed(ctx: *mut ZkCtx, crs: *const ZkCrs, inputs: *const u64, n_inputs: usize, proofs: *const u8, n_proofs: usize,
                                   ok: *mut c_int) -> c_int;
+    // the verifying key: host object (no context) + the batch calls with the key in the place of the CRS
+    fn zk_vk_create(desc: *const ZkVkDesc, out: *mut *mut ZkVk) -> c_int;
+    fn zk_vk_from_crs(ctx: *mut ZkCtx, crs: *const ZkCrs, out: *mut *mut ZkVk) -> c_int;
+    fn zk_vk_free(vk: *mut ZkVk);
+    fn zk_vk_dims(vk: *const ZkVk, input: *mut usize) -> c_int;
+    fn zk_vk_bytes(input: usize) -> usize;
+    fn zk_vk_to_bytes(vk: *const ZkVk, out: *mut u8, len: usize) -> c_int;
+    fn zk_vk_from_bytes(input: *const u8, len: usize, out: *mut *mut ZkVk) -> c_int;
+    fn zk_vk_save(vk: *const ZkVk, path: *const c_char) -> c_int;
+    fn zk_vk_load(path: *const c_char, out: *mut *mut ZkVk) -> c_int;
+    fn zk_vk_verify(vk: *const ZkVk, inputs: *const u64, n_inputs: usize, proof: *const u8, ok: *mut c_int) -> c_int;
+    fn zk_vk_verify_batch(ctx: *mut ZkCtx, vk: *mut ZkVk, inputs: *const u64, n_inputs: usize, proofs: *const u8, n_proofs: usize,
+                          ok: *mut c_int) -> c_int;
+    fn zk_vk_verify_batch_compressed(ctx: *mut ZkCtx, vk: *mut ZkVk, inputs: *const u64, n_inputs: usize, proofs: *const u8, n_proofs: usize,
+                                     ok: *mut c_int) -> c_int;
+    fn zk_vk_verify_batch_all(ctx: *mut ZkCtx, vk: *mut ZkVk, inputs: *const u64, n_inputs: usize, proofs: *const u8, n_proofs: usize,
+                              z: *const u64, ok: *mut c_int) -> c_int;
+    fn zk_vk_input_sums(ctx: *mut ZkCtx, vk: *mut ZkVk, inputs: *const u64, n_inputs: usize, n: usize, tables: c_int, out: *mut u64) -> c_int;
     // the 259-byte proof <-> the compressed 128-byte form: on the host (no context), or for n proofs on the GPU
     fn zk_proof_compress(proof: *const u8, out: *mut u8) -> c_int;
     fn zk_proof_decompress(input: *const u8, proof_out: *mut u8) -> c_int;
@@ -680,7 +706,100 @@ impl GpuProver {
         out
     }
     pub fn dims(&self) -> (usize, usize, usize) { (self.n, self.m, self.input) }
+    /// the verifying key of the device CRS (zk_vk_from_crs)
+    pub fn verifying_key(&self) -> VerifyingKey { VerifyingKey::from_crs(self) }
 }
+
+/// The verifying key (zk_vk): alpha, beta, gamma, delta and sum_gamma[0..l], all groth16::verify reads of (SigmaG1, SigmaG2).  Host
+/// data: to_bytes / from_bytes / verify need no GPU.  verify_batch runs on a GpuProver's context; the first call binds the key to it.
+pub struct VerifyingKey(*mut ZkVk);
+impl VerifyingKey {
+    pub fn from_crs(p: &GpuProver) -> Self {
+        let mut k = std::ptr::null_mut();
+        unsafe { check(p.ctx.0, zk_vk_from_crs(p.ctx.0, p.crs, &mut k)); }
+        VerifyingKey(k)
+    }
+    /// from the reference's own types; panics on a point off its curve or outside G2 (ZK_ERR_RANGE)
+    pub fn new(sigma: (&SigmaG1<G1Local>, &SigmaG2<G2Local>)) -> Self {
+        let (a1, sg) = (g1_to_words(&sigma.0.alpha), g1s(&sigma.0.sum_gamma));
+        let (b2, g2, d2) = (g2_to_words(&sigma.1.beta), g2_to_words(&sigma.1.gamma), g2_to_words(&sigma.1.delta));
+        let desc = ZkVkDesc { input: sigma.0.sum_gamma.len() - 1, alpha_g1: a1.as_ptr(),
+            beta_g2: b2.as_ptr(), gamma_g2: g2.as_ptr(), delta_g2: d2.as_ptr(), sum_gamma_g1: sg.as_ptr() };
+        let mut k = std::ptr::null_mut();
+        assert_eq!(unsafe { zk_vk_create(&desc, &mut k) }, 0, "zk_vk_create failed");
+        VerifyingKey(k)
+    }
+    pub fn input(&self) -> usize {
+        let mut l = 0usize;
+        assert_eq!(unsafe { zk_vk_dims(self.0, &mut l) }, 0);
+        l
+    }
+    /// the ZKVKv1 byte form (include/zkgpu.h)
+    pub fn to_bytes(&self) -> Vec<u8> {
+        let mut out = vec![0u8; unsafe { zk_vk_bytes(self.input()) }];
+        assert_eq!(unsafe { zk_vk_to_bytes(self.0, out.as_mut_ptr(), out.len()) }, 0);
+        out
+    }
+    /// Err(status): ZK_ERR_IO (-8) for a wrong length, magic or checksum, ZK_ERR_RANGE (-6) for a bad point
+    pub fn from_bytes(bytes: &[u8]) -> Result<Self, c_int> {
+        let mut k = std::ptr::null_mut();
+        match unsafe { zk_vk_from_bytes(bytes.as_ptr(), bytes.len(), &mut k) } { 0 => Ok(VerifyingKey(k)), rc => Err(rc) }
+    }
+    pub fn save(&self, path: &str) -> Result<(), c_int> {
+        let p = std::ffi::CString::new(path).unwrap();
+        match unsafe { zk_vk_save(self.0, p.as_ptr()) } { 0 => Ok(()), rc => Err(rc) }
+    }
+    pub fn load(path: &str) -> Result<Self, c_int> {
+        let p = std::ffi::CString::new(path).unwrap();
+        let mut k = std::ptr::null_mut();
+        match unsafe { zk_vk_load(p.as_ptr(), &mut k) } { 0 => Ok(VerifyingKey(k)), rc => Err(rc) }
+    }
+    /// groth16::verify on the host, no GPU; panics on an input >= r as the reference's FrLocal arithmetic would
+    pub fn verify(&self, inputs: &[FrLocal], proof: &Proof<G1Local, G2Local>) -> bool {
+        let (x, bytes, mut ok) = (frs(inputs), proof_to_bytes(proof), 0 as c_int);
+        assert_eq!(unsafe { zk_vk_verify(self.0, x.as_ptr(), inputs.len(), bytes.as_ptr(), &mut ok) }, 0, "zk_vk_verify failed");
+        ok == 1
+    }
+    /// GpuProver::verify_batch with the key in the place of the CRS (zk_vk_verify_batch), on `p`'s context
+    pub fn verify_batch(&self, p: &GpuProver, inputs: &[Vec<FrLocal>], proofs: &[Proof<G1Local, G2Local>]) -> Vec<bool> {
+        assert!(inputs.len() == proofs.len(), "one input row per proof");
+        let k = inputs.first().map_or(0, |r| r.len());
+        assert!(inputs.iter().all(|r| r.len() == k), "every proof needs the same number of inputs");
+        let x: Vec<u64> = inputs.iter().flat_map(|r| frs(r)).collect();
+        let bytes: Vec<u8> = proofs.iter().flat_map(|q| proof_to_bytes(q).to_vec()).collect();
+        let mut ok = vec![0 as c_int; proofs.len()];
+        unsafe { check(p.ctx.0, zk_vk_verify_batch(p.ctx.0, self.0, x.as_ptr(), k, bytes.as_ptr(), proofs.len(), ok.as_mut_ptr())); }
+        ok.into_iter().map(|v| v == 1).collect()
+    }
+    /// the compressed and the one-verdict forms, and the input sums on their own
+    pub fn verify_batch_compressed(&self, p: &GpuProver, inputs: &[Vec<FrLocal>], proofs: &[[u8; 128]]) -> Vec<bool> {
+        let k = inputs.first().map_or(0, |r| r.len());
+        let x: Vec<u64> = inputs.iter().flat_map(|r| frs(r)).collect();
+        let bytes: Vec<u8> = proofs.iter().flat_map(|q| q.to_vec()).collect();
+        let mut ok = vec![0 as c_int; proofs.len()];
+        unsafe { check(p.ctx.0, zk_vk_verify_batch_compressed(p.ctx.0, self.0, x.as_ptr(), k, bytes.as_ptr(), proofs.len(), ok.as_mut_ptr())); }
+        ok.into_iter().map(|v| v == 1).collect()
+    }
+    pub fn verify_batch_all(&self, p: &GpuProver, inputs: &[Vec<FrLocal>], proofs: &[Proof<G1Local, G2Local>], z: &[[u64; 2]]) -> bool {
+        assert!(inputs.len() == proofs.len() && z.len() == proofs.len(), "one input row and one multiplier per proof");
+        let k = inputs.first().map_or(0, |r| r.len());
+        let x: Vec<u64> = inputs.iter().flat_map(|r| frs(r)).collect();
+        let bytes: Vec<u8> = proofs.iter().flat_map(|q| proof_to_bytes(q).to_vec()).collect();
+        let zw: Vec<u64> = z.iter().flat_map(|v| v.to_vec()).collect();
+        let mut ok: c_int = 0;
+        unsafe { check(p.ctx.0, zk_vk_verify_batch_all(p.ctx.0, self.0, x.as_ptr(), k, bytes.as_ptr(), proofs.len(), zw.as_ptr(), &mut ok)); }
+        ok == 1
+    }
+    pub fn input_sums(&self, p: &GpuProver, inputs: &[Vec<FrLocal>], tables: bool) -> Vec<G1Local> {
+        let k = inputs.first().map_or(0, |r| r.len());
+        let x: Vec<u64> = inputs.iter().flat_map(|r| frs(r)).collect();
+        let mut out = vec![0u64; 8 * inputs.len()];
+        unsafe { check(p.ctx.0, zk_vk_input_sums(p.ctx.0, self.0, x.as_ptr(), k, inputs.len(), tables as c_int, out.as_mut_ptr())); }
+        out.chunks(8).map(g1_from_words).collect()
+    }
+}
+impl Drop for VerifyingKey { fn drop(&mut self) { unsafe { zk_vk_free(self.0) } } }   // safe before or after the prover's context goes
+
 impl Drop for GpuProver {
     fn drop(&mut self) { unsafe { zk_crs_free(self.crs); zk_qap_free(self.qap); } }   // self.ctx drops afterwards (field order)
 }

@@ -94,7 +94,7 @@ const char* zk_last_error(const zk_ctx* ctx);          /* detail of the last fai
  * over the table xi_t | xi | sum_delta with one set of buckets and one reduction tail; 0 = two products as in round 4; same proof
  * bytes, +1.3 % proofs/s at 2^20 gates, profiles/r5_experiments.txt item 2), "witgen_scratch_kib" (read by zk_witgen_create: how much
  * device memory, in KiB, that generator may hold for slot values; default 8388608 = 8 GiB), "qap_check_chunk" and
- * "qap_check_by_instance" (see zk_qap_check).  Each is exercised by a -m gpu test.  Unknown keys are
+ * "qap_check_by_instance" (see zk_qap_check), "vk_table_kib" (see zk_vk_verify_batch).  Each is exercised by a -m gpu test.  Unknown keys are
  * answered with ZK_ERR_UNSUPPORTED.  Measurement entry points and switches -- kernel event timing, the tuning keys of bench.py --opt /
  * --serialize -- are NOT part of this header: include/zkgpu_measure.h. */
 int zk_set_option(zk_ctx* ctx, const char* key, long value);
@@ -583,6 +583,64 @@ int zk_verify_batch_all(zk_ctx* ctx, const zk_crs* crs, const uint64_t* inputs, 
  * Fq12 = Fq6[w]/(w^2 - v), Fq6 = Fq2[v]/(v^3 - (9+i)).  Host only; needs no context.  ZK_ERR_RANGE when a coordinate
  * is >= q, a point is off its curve or g2 is outside the order-r subgroup. */
 int zk_pairing(const uint64_t g1[ZK_G1_WORDS], const uint64_t g2[ZK_G2_WORDS], uint64_t out[48]);
+
+/* ------------------------------------------------------------------------------------------
+ * verifying key: what groth16::verify reads of (SigmaG1, SigmaG2) (groth16/mod.rs:299-320: alpha, beta, gamma, delta and the
+ * l + 1 points of sum_gamma), as an object of its own -- a verifier needs neither the proving key nor, for one proof, a GPU.
+ * The reference has no such type: its verify takes the whole (SigmaG1, SigmaG2).
+ * ---------------------------------------------------------------------------------------- */
+typedef struct zk_vk zk_vk;
+typedef struct {
+    size_t input;                  /* l */
+    const uint64_t* alpha_g1;      /* 8 words */
+    const uint64_t *beta_g2, *gamma_g2, *delta_g2;   /* 16 words each */
+    const uint64_t* sum_gamma_g1;  /* (l + 1) x 8 words, wires 0..l */
+} zk_vk_desc;
+/* The object is host data; the calls of this first group need no context (as zk_pairing / zk_proof_compress).
+ * zk_vk_create: every point goes through zk_verify's readers (coordinates < q, on the curve, G2 points in the order-r subgroup;
+ * infinity = all zero is legal); a failing point: ZK_ERR_RANGE and *out = NULL; an l the host has no memory for: ZK_ERR_SIZE.  What depends only on the points -- the lines of
+ * beta, gamma and delta and ml(alpha, beta) -- is computed here, once.
+ * Byte form (zk_vk_to_bytes and the file of zk_vk_save are the same bytes): "ZKVKv1\0\0" | l as u64 LE | FNV-1a-64 of the payload
+ * as u64 LE (the checksum of ZKCRSv1) | payload = alpha_g1 | beta_g2 | gamma_g2 | delta_g2 | sum_gamma_g1[0..l] as canonical
+ * little-endian words; zk_vk_bytes(l) = 24 + 8 (56 + 8 (l + 1)).  zk_vk_to_bytes needs len >= zk_vk_bytes(l) and writes exactly
+ * that many.  zk_vk_from_bytes / zk_vk_load: ZK_ERR_IO for a wrong length, magic or checksum or a missing file, ZK_ERR_RANGE for a
+ * point zk_vk_create would refuse; to_bytes(from_bytes(b)) == b.
+ * zk_vk_verify: *ok and the status are zk_verify's for every proof and input row (the row is truncated to min(l, n_inputs) the
+ * same way, an input >= r among those read gives ZK_ERR_RANGE), without a context and without a GPU.
+ * A null pointer: ZK_ERR_ARG, nothing written.  zk_vk_free(NULL) is a no-op. */
+int zk_vk_create(const zk_vk_desc* desc, zk_vk** out);
+void zk_vk_free(zk_vk* vk);
+int zk_vk_dims(const zk_vk* vk, size_t* input);
+size_t zk_vk_bytes(size_t input);
+int zk_vk_to_bytes(const zk_vk* vk, uint8_t* out, size_t len);
+int zk_vk_from_bytes(const uint8_t* in, size_t len, zk_vk** out);
+int zk_vk_save(const zk_vk* vk, const char* path);
+int zk_vk_load(const char* path, zk_vk** out);
+int zk_vk_verify(const zk_vk* vk, const uint64_t* inputs, size_t n_inputs, const uint8_t proof[ZK_PROOF_BYTES], int* ok);
+/* The key of a device CRS: the points are copied on zk_verify_batch's stream (an outstanding zk_prove_submit ticket is neither
+ * waited for nor disturbed) and go through zk_vk_create. */
+int zk_vk_from_crs(zk_ctx* ctx, const zk_crs* crs, zk_vk** out);
+/* Batch verification over a key: zk_verify_batch, zk_verify_batch_compressed and zk_verify_batch_all with the key in the place of
+ * the CRS.  Verdicts, statuses, error texts, chunking, stream and device buffers are exactly those calls' (see there); only the
+ * re-check of the CRS points has no counterpart, a key's points were checked when it was made.
+ * On its first batch call a key BINDS to that context: its constants are uploaded once, on the verify stream, and stay resident;
+ * a later batch call with another context (or after that context was destroyed) gives ZK_ERR_ARG.  zk_vk_free and
+ * zk_ctx_destroy are safe in either order.  The device memory of a key freed first (constants and tables) is parked, not freed --
+ * freeing would wait for an outstanding proof ticket -- and goes with the context: a long-lived context that binds and frees
+ * many keys should re-use keys, or be re-created now and then.  The input sums S_j = sum_gamma_0 + sum_i x_ji sum_gamma_i are formed from per-key
+ * window tables (4-bit unsigned digits: 60 KiB of device memory per input, built on the first call that may use them) unless
+ * the tables would exceed the option "vk_table_kib" (KiB; default 65536; 0 = never), the device has no memory for them, or l = 0: then zk_verify_batch's kernel
+ * runs on the key's resident bases.  That is a memory condition; the verdicts never depend on it. */
+int zk_vk_verify_batch(zk_ctx* ctx, zk_vk* vk, const uint64_t* inputs, size_t n_inputs, const uint8_t* proofs, size_t n_proofs, int* ok);
+int zk_vk_verify_batch_compressed(zk_ctx* ctx, zk_vk* vk, const uint64_t* inputs, size_t n_inputs, const uint8_t* proofs,
+                                  size_t n_proofs, int* ok);
+int zk_vk_verify_batch_all(zk_ctx* ctx, zk_vk* vk, const uint64_t* inputs, size_t n_inputs, const uint8_t* proofs, size_t n_proofs,
+                           const uint64_t* z, int* ok);
+/* The input sums on their own (the building block behind the batch calls, as zk_msm_g1 is behind zk_prove): out[j] = S_j for
+ * j < n, 8 canonical words each (infinity = all zero); inputs: n rows of n_inputs Fr values, of which the first min(l, n_inputs)
+ * are read.  tables = 0 runs zk_verify_batch's bit-serial kernel, tables = 1 the table kernel; the words are the same.
+ * tables = 1 on a key whose tables exceed "vk_table_kib" (or found no device memory): ZK_ERR_SIZE.  An input >= r: ZK_ERR_RANGE.  n == 0: ZK_OK. */
+int zk_vk_input_sums(zk_ctx* ctx, zk_vk* vk, const uint64_t* inputs, size_t n_inputs, size_t n, int tables, uint64_t* out);
 
 #ifdef __cplusplus
 }

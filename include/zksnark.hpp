@@ -408,5 +408,133 @@ inline bool verify_batch_all(const Context& c, const Sigma& sigma, const std::ve
     return verify_batch_all_with(c, sigma, inputs, proofs, z);
 }
 
+// The verifying key (zk_vk): alpha, beta, gamma, delta and sum_gamma[0..l], all groth16::verify reads of (SigmaG1, SigmaG2).
+// Host data: from_points / from_bytes / load / to_bytes / save / verify need no Context and no GPU.  The batch calls take a
+// Context; the first one binds the key to it (a later call with another Context throws ZK_ERR_ARG).  Key and Context may be
+// destroyed in either order.
+class VerifyingKey {
+   public:
+    VerifyingKey(VerifyingKey&& o) noexcept : k_(std::exchange(o.k_, nullptr)) {}
+    VerifyingKey(const VerifyingKey&) = delete;
+    ~VerifyingKey() { zk_vk_free(k_); }
+    zk_vk* get() const { return k_; }
+    // points as canonical little-endian words: 8, 16, 16, 16 and (l + 1) x 8
+    static VerifyingKey from_points(const std::vector<uint64_t>& alpha_g1, const std::vector<uint64_t>& beta_g2, const std::vector<uint64_t>& gamma_g2,
+                                    const std::vector<uint64_t>& delta_g2, const std::vector<uint64_t>& sum_gamma_g1) {
+        if (alpha_g1.size() != 8 || beta_g2.size() != 16 || gamma_g2.size() != 16 || delta_g2.size() != 16 || sum_gamma_g1.size() < 8 ||
+            sum_gamma_g1.size() % 8)
+            throw Error(ZK_ERR_ARG, "VerifyingKey::from_points: 8, 16, 16, 16 and (l + 1) x 8 words");
+        const zk_vk_desc d{sum_gamma_g1.size() / 8 - 1, alpha_g1.data(), beta_g2.data(), gamma_g2.data(), delta_g2.data(), sum_gamma_g1.data()};
+        zk_vk* k = nullptr;
+        host(zk_vk_create(&d, &k), "VerifyingKey::from_points");
+        return VerifyingKey(k);
+    }
+    static VerifyingKey from_sigma(const Context& c, const Sigma& sigma) {
+        zk_vk* k = nullptr;
+        c.check(zk_vk_from_crs(c.get(), sigma.get(), &k), "VerifyingKey::from_sigma");
+        return VerifyingKey(k);
+    }
+    static VerifyingKey from_bytes(const std::vector<uint8_t>& b) {
+        zk_vk* k = nullptr;
+        const uint8_t none = 0;
+        host(zk_vk_from_bytes(b.empty() ? &none : b.data(), b.size(), &k), "VerifyingKey::from_bytes");
+        return VerifyingKey(k);
+    }
+    static VerifyingKey load(const std::string& path) {
+        zk_vk* k = nullptr;
+        host(zk_vk_load(path.c_str(), &k), "VerifyingKey::load");
+        return VerifyingKey(k);
+    }
+    size_t input() const {
+        size_t l = 0;
+        host(zk_vk_dims(k_, &l), "VerifyingKey::input");
+        return l;
+    }
+    std::vector<uint8_t> to_bytes() const {
+        std::vector<uint8_t> b(zk_vk_bytes(input()));
+        host(zk_vk_to_bytes(k_, b.data(), b.size()), "VerifyingKey::to_bytes");
+        return b;
+    }
+    void save(const std::string& path) const { host(zk_vk_save(k_, path.c_str()), "VerifyingKey::save"); }
+    // groth16::verify on the host: the verdict of verify(c, sigma, inputs, proof)
+    bool verify(const std::vector<FrLocal>& inputs, const Proof& proof) const {
+        int ok = 0;
+        host(zk_vk_verify(k_, inputs.empty() ? nullptr : inputs[0].w.data(), inputs.size(), proof.bytes.data(), &ok), "VerifyingKey::verify");
+        return ok != 0;
+    }
+    // the batch calls of groth16:: with the key in the place of sigma
+    std::vector<bool> verify_batch(const Context& c, const std::vector<std::vector<FrLocal>>& inputs, const std::vector<Proof>& proofs) const {
+        std::vector<uint64_t> x;
+        const size_t k = pack(inputs, proofs.size(), x, "VerifyingKey::verify_batch");
+        std::vector<uint8_t> bytes(proofs.size() * ZK_PROOF_BYTES + 1);
+        for (size_t j = 0; j < proofs.size(); ++j) std::copy(proofs[j].bytes.begin(), proofs[j].bytes.end(), bytes.begin() + j * ZK_PROOF_BYTES);
+        std::vector<int> ok(proofs.size(), 0);
+        c.check(zk_vk_verify_batch(c.get(), k_, k ? x.data() : nullptr, k, bytes.data(), proofs.size(), ok.data()), "VerifyingKey::verify_batch");
+        return std::vector<bool>(ok.begin(), ok.end());
+    }
+    std::vector<bool> verify_batch_compressed(const Context& c, const std::vector<std::vector<FrLocal>>& inputs,
+                                              const std::vector<CompressedProof>& proofs) const {
+        std::vector<uint64_t> x;
+        const size_t k = pack(inputs, proofs.size(), x, "VerifyingKey::verify_batch_compressed");
+        std::vector<uint8_t> bytes(proofs.size() * ZK_PROOF_COMPRESSED_BYTES + 1);
+        for (size_t j = 0; j < proofs.size(); ++j)
+            std::copy(proofs[j].bytes.begin(), proofs[j].bytes.end(), bytes.begin() + j * ZK_PROOF_COMPRESSED_BYTES);
+        std::vector<int> ok(proofs.size(), 0);
+        c.check(zk_vk_verify_batch_compressed(c.get(), k_, k ? x.data() : nullptr, k, bytes.data(), proofs.size(), ok.data()),
+                "VerifyingKey::verify_batch_compressed");
+        return std::vector<bool>(ok.begin(), ok.end());
+    }
+    bool verify_batch_all_with(const Context& c, const std::vector<std::vector<FrLocal>>& inputs, const std::vector<Proof>& proofs,
+                               const std::vector<std::array<uint64_t, 2>>& z) const {
+        if (z.size() != proofs.size()) throw Error(ZK_ERR_ARG, "VerifyingKey::verify_batch_all: one multiplier per proof");
+        std::vector<uint64_t> x, zw(2 * proofs.size() + 2);
+        const size_t k = pack(inputs, proofs.size(), x, "VerifyingKey::verify_batch_all");
+        std::vector<uint8_t> bytes(proofs.size() * ZK_PROOF_BYTES + 1);
+        for (size_t j = 0; j < proofs.size(); ++j) {
+            std::copy(proofs[j].bytes.begin(), proofs[j].bytes.end(), bytes.begin() + j * ZK_PROOF_BYTES);
+            zw[2 * j] = z[j][0];
+            zw[2 * j + 1] = z[j][1];
+        }
+        int ok = 0;
+        c.check(zk_vk_verify_batch_all(c.get(), k_, k ? x.data() : nullptr, k, bytes.data(), proofs.size(), zw.data(), &ok),
+                "VerifyingKey::verify_batch_all");
+        return ok != 0;
+    }
+    bool verify_batch_all(const Context& c, const std::vector<std::vector<FrLocal>>& inputs, const std::vector<Proof>& proofs) const {
+        static thread_local std::random_device rd;
+        std::vector<std::array<uint64_t, 2>> z(proofs.size());
+        for (auto& zj : z)
+            do {
+                for (auto& w : zj) w = ((uint64_t)rd() << 32) | rd();
+            } while (!(zj[0] | zj[1]));
+        return verify_batch_all_with(c, inputs, proofs, z);
+    }
+    // S_j = sum_gamma_0 + sum_i inputs[j][i] sum_gamma_i as 8 canonical words per row (zk_vk_input_sums); tables = false runs
+    // verify_batch's bit-serial kernel, true the key's window tables: the same words
+    std::vector<uint64_t> input_sums(const Context& c, const std::vector<std::vector<FrLocal>>& inputs, bool tables = true) const {
+        std::vector<uint64_t> x, out(inputs.size() * 8);
+        const size_t k = pack(inputs, inputs.size(), x, "VerifyingKey::input_sums");
+        c.check(zk_vk_input_sums(c.get(), k_, k ? x.data() : nullptr, k, inputs.size(), tables ? 1 : 0, out.data()), "VerifyingKey::input_sums");
+        return out;
+    }
+
+   private:
+    explicit VerifyingKey(zk_vk* k) : k_(k) {}
+    static void host(int st, const char* where) {
+        if (st != ZK_OK) throw Error(st, where);
+    }
+    static size_t pack(const std::vector<std::vector<FrLocal>>& inputs, size_t n, std::vector<uint64_t>& x, const char* where) {
+        if (inputs.size() != n) throw Error(ZK_ERR_ARG, std::string(where) + ": one input row per proof");
+        const size_t k = n ? inputs[0].size() : 0;
+        x.assign(n * k * 4, 0);
+        for (size_t j = 0; j < n; ++j) {
+            if (inputs[j].size() != k) throw Error(ZK_ERR_ARG, std::string(where) + ": every proof needs the same number of inputs");
+            for (size_t i = 0; i < k; ++i) std::copy(inputs[j][i].w.begin(), inputs[j][i].w.end(), x.begin() + (j * k + i) * 4);
+        }
+        return k;
+    }
+    zk_vk* k_;
+};
+
 }  // namespace groth16
 }  // namespace zksnark

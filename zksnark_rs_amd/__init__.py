@@ -25,7 +25,7 @@ Q_MODULUS = 21888242871839275222246405745257275088696311157297823662689037894645
 
 __all__ = ["Context", "ZkError", "fr_to_limbs", "limbs_to_int", "ints_to_limbs", "limbs_to_ints",
            "PROOF_BYTES", "PARTIAL_BYTES", "MAX_IN_FLIGHT", "MAX_BATCH", "R_MODULUS", "Q_MODULUS", "SplitMix64", "pairing", "proof_save", "proof_load",
-           "PROOF_COMPRESSED_BYTES", "proof_compress", "proof_decompress"]
+           "PROOF_COMPRESSED_BYTES", "proof_compress", "proof_decompress", "VerifyingKey"]
 
 
 class ZkError(RuntimeError):
@@ -635,13 +635,9 @@ class Context:
         valid encoding gives ok = False and 259 bytes of 0xFF."""
         return self._codec_batch(self.lib.zk_proof_decompress_batch, compressed, PROOF_COMPRESSED_BYTES, PROOF_BYTES, "proof_decompress_batch")
 
-    def verify_batch_all(self, crs, inputs, proofs, z=None):
-        """zk_verify_batch_all: one verdict for the whole batch -> True iff every proof decodes and the random linear combination
-        of their pairing equations with multipliers z holds (inputs and proofs as in verify_batch).  z: N non-zero 128-bit
-        multipliers (ints, or an (N, 2) uint64 array of little-endian words); None draws them from os.urandom.  A batch with
-        a bad proof passes only for z in a set of density <= 1 / (2^128 - 1), so z must be secret to whoever made the proofs."""
-        a, pb = self._batch_args(inputs, proofs, "verify_batch_all")
-        n = pb.shape[0]
+    @staticmethod
+    def _z_words(z, n):
+        """the multipliers of verify_batch_all as an (n, 2) uint64 array; None draws them from os.urandom"""
         if z is None:
             zw = np.frombuffer(os.urandom(16 * n), dtype=np.uint64).reshape(n, 2).copy()
             for j in np.flatnonzero((zw == 0).all(axis=1)):
@@ -656,10 +652,26 @@ class Context:
             zw = np.array([[v & (2**64 - 1), v >> 64] for v in zs], dtype=np.uint64).reshape(-1, 2)
         if zw.shape[0] != n:
             raise ValueError("verify_batch_all: z must hold one multiplier per proof")
+        return zw
+
+    def verify_batch_all(self, crs, inputs, proofs, z=None):
+        """zk_verify_batch_all: one verdict for the whole batch -> True iff every proof decodes and the random linear combination
+        of their pairing equations with multipliers z holds (inputs and proofs as in verify_batch).  z: N non-zero 128-bit
+        multipliers (ints, or an (N, 2) uint64 array of little-endian words); None draws them from os.urandom.  A batch with
+        a bad proof passes only for z in a set of density <= 1 / (2^128 - 1), so z must be secret to whoever made the proofs."""
+        a, pb = self._batch_args(inputs, proofs, "verify_batch_all")
+        n = pb.shape[0]
+        zw = self._z_words(z, n)
         ok = C.c_int(0)
         self._check(self.lib.zk_verify_batch_all(self.ptr, crs.ptr, a.ctypes.data_as(_lib.u64p) if a.size else None, a.shape[1],
                                                  pb.ctypes.data_as(_lib.u8p), n, zw.ctypes.data_as(_lib.u64p), C.byref(ok)))
         return bool(ok.value)
+
+    def verifying_key(self, crs):
+        """zk_vk_from_crs: the VerifyingKey of a device CRS (the points are copied on the verify stream)."""
+        p = C.c_void_p()
+        self._check(self.lib.zk_vk_from_crs(self.ptr, crs.ptr, C.byref(p)))
+        return VerifyingKey(p, self)
 
     # ---- profiling ----
     def profile_reset(self):
@@ -683,3 +695,140 @@ class Context:
         """What every inner product since the last msm_plan_reset decided from its size: a list of dicts with the fields
         zkgpu_measure.h lists, in the order the host enqueued the products."""
         return [{f: self.get_option("msm_plan.%d.%s" % (i, f)) for f in self.MSM_PLAN_FIELDS} for i in range(self.get_option("msm_plan_count"))]
+
+
+class VerifyingKey:
+    """zk_vk: what groth16::verify reads of the CRS (alpha, beta, gamma, delta, sum_gamma[0..l]) as an object of its own.  The
+    object is host data: from_points / from_bytes / load / to_bytes / save / verify need neither a Context nor a GPU.  The batch
+    calls take a Context; the first one binds the key to it (constants and input-sum tables stay resident on that device)."""
+
+    def __init__(self, ptr, ctx=None):
+        """ptr: a zk_vk*; ctx: the Context this key's batch calls are meant for (see the `ctx` attribute)"""
+        self.lib = _lib.load()
+        self.ptr = ptr
+        #: the Context that groth16.verify_batch* run this key on, or None.  Context.verifying_key and groth16.verifying_key set
+        #: it; from_points / from_bytes / load take it as an argument, and it may be assigned later.  The methods of this class
+        #: take their Context explicitly and do not read it.
+        self.ctx = ctx
+
+    @staticmethod
+    def _new(rc, p, what, ctx=None):
+        if rc != 0:
+            raise ZkError(rc, what)
+        return VerifyingKey(p, ctx)
+
+    @classmethod
+    def from_points(cls, alpha_g1, beta_g2, gamma_g2, delta_g2, sum_gamma_g1, ctx=None):
+        """zk_vk_create: limb arrays as everywhere in the ABI -- (8,), (16,) x 3 and (l + 1, 8).  ZkError(ZK_ERR_RANGE) for a
+        point out of range, off its curve or (G2) outside the order-r subgroup."""
+        a, ap = _u64(np.asarray(alpha_g1).reshape(8))
+        b, bp = _u64(np.asarray(beta_g2).reshape(16))
+        g, gp = _u64(np.asarray(gamma_g2).reshape(16))
+        d, dp = _u64(np.asarray(delta_g2).reshape(16))
+        sg, sgp = _u64(np.asarray(sum_gamma_g1).reshape(-1, 8))
+        if sg.shape[0] < 1:
+            raise ValueError("VerifyingKey.from_points: sum_gamma holds l + 1 >= 1 points")
+        desc = _lib.VkDesc(sg.shape[0] - 1, ap, bp, gp, dp, sgp)
+        p = C.c_void_p()
+        return cls._new(_lib.load().zk_vk_create(C.byref(desc), C.byref(p)), p, "VerifyingKey.from_points", ctx)
+
+    @classmethod
+    def from_bytes(cls, data, ctx=None):
+        """zk_vk_from_bytes: ZkError(ZK_ERR_IO) for a wrong length, magic or checksum, ZK_ERR_RANGE for a bad point."""
+        data = bytes(data)
+        buf = np.frombuffer(data or b"\0", dtype=np.uint8).copy()      # an empty string still needs a pointer
+        p = C.c_void_p()
+        return cls._new(_lib.load().zk_vk_from_bytes(buf.ctypes.data_as(_lib.u8p), len(data), C.byref(p)), p, "VerifyingKey.from_bytes", ctx)
+
+    @classmethod
+    def load(cls, path, ctx=None):
+        p = C.c_void_p()
+        return cls._new(_lib.load().zk_vk_load(str(path).encode(), C.byref(p)), p, "VerifyingKey.load", ctx)
+
+    def close(self):
+        if getattr(self, "ptr", None):
+            self.lib.zk_vk_free(self.ptr)
+            self.ptr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def input(self):
+        l = C.c_size_t(0)
+        rc = self.lib.zk_vk_dims(self.ptr, C.byref(l))
+        if rc != 0:
+            raise ZkError(rc)
+        return int(l.value)
+
+    def to_bytes(self):
+        out = np.zeros(int(self.lib.zk_vk_bytes(self.input)), dtype=np.uint8)
+        rc = self.lib.zk_vk_to_bytes(self.ptr, out.ctypes.data_as(_lib.u8p), out.size)
+        if rc != 0:
+            raise ZkError(rc)
+        return out.tobytes()
+
+    def save(self, path):
+        rc = self.lib.zk_vk_save(self.ptr, str(path).encode())
+        if rc != 0:
+            raise ZkError(rc, "VerifyingKey.save")
+
+    def verify(self, inputs, proof):
+        """zk_vk_verify: groth16::verify on the host, no Context: the verdict Context.verify gives over the CRS."""
+        a = ints_to_limbs(list(inputs)) if not isinstance(inputs, np.ndarray) else np.ascontiguousarray(inputs, dtype=np.uint64).reshape(-1, 4)
+        pb = np.frombuffer(bytes(proof), dtype=np.uint8).copy()
+        if pb.size != PROOF_BYTES:
+            raise ValueError("VerifyingKey.verify: a proof is %d bytes" % PROOF_BYTES)
+        ok = C.c_int(0)
+        rc = self.lib.zk_vk_verify(self.ptr, a.ctypes.data_as(_lib.u64p) if a.size else None, a.shape[0], pb.ctypes.data_as(_lib.u8p), C.byref(ok))
+        if rc != 0:
+            raise ZkError(rc, "VerifyingKey.verify")
+        return bool(ok.value)
+
+    # ---- on a Context ----
+    def _batch(self, fn, ctx, inputs, proofs, name, width):
+        a, pb = Context._batch_args(inputs, proofs, name, width)
+        n = pb.shape[0]
+        ok = np.zeros(n, dtype=np.int32)
+        ctx._check(fn(ctx.ptr, self.ptr, a.ctypes.data_as(_lib.u64p) if a.size else None, a.shape[1], pb.ctypes.data_as(_lib.u8p), n,
+                      ok.ctypes.data_as(C.POINTER(C.c_int))))
+        return ok.astype(bool)
+
+    def verify_batch(self, ctx, inputs, proofs):
+        """zk_vk_verify_batch: Context.verify_batch with the key in the place of the CRS -> (N,) bool array."""
+        return self._batch(self.lib.zk_vk_verify_batch, ctx, inputs, proofs, "verify_batch", PROOF_BYTES)
+
+    def verify_batch_compressed(self, ctx, inputs, proofs):
+        """zk_vk_verify_batch_compressed: the same over 128-byte proofs."""
+        return self._batch(self.lib.zk_vk_verify_batch_compressed, ctx, inputs, proofs, "verify_batch_compressed", PROOF_COMPRESSED_BYTES)
+
+    def verify_batch_all(self, ctx, inputs, proofs, z=None):
+        """zk_vk_verify_batch_all: Context.verify_batch_all with the key in the place of the CRS -> one bool."""
+        a, pb = Context._batch_args(inputs, proofs, "verify_batch_all")
+        n = pb.shape[0]
+        zw = Context._z_words(z, n)
+        ok = C.c_int(0)
+        ctx._check(self.lib.zk_vk_verify_batch_all(ctx.ptr, self.ptr, a.ctypes.data_as(_lib.u64p) if a.size else None, a.shape[1],
+                                                   pb.ctypes.data_as(_lib.u8p), n, zw.ctypes.data_as(_lib.u64p), C.byref(ok)))
+        return bool(ok.value)
+
+    def input_sums(self, ctx, inputs, tables=True):
+        """zk_vk_input_sums: S_j = sum_gamma_0 + sum_i x_ji sum_gamma_i for every row of `inputs` ((N, k) ints or (N, k, 4)
+        limbs) -> (N, 8) uint64 array of affine points (infinity = zeros).  tables=False runs verify_batch's bit-serial kernel,
+        tables=True the key's window tables; the words are the same."""
+        if isinstance(inputs, np.ndarray) and inputs.ndim == 3:
+            a = np.ascontiguousarray(inputs, dtype=np.uint64)
+        else:
+            rows = [[int(x) for x in r] for r in inputs]
+            k = len(rows[0]) if rows else 0
+            if any(len(r) != k for r in rows):
+                raise ValueError("input_sums: every row needs the same number of inputs")
+            a = ints_to_limbs([x for r in rows for x in r]).reshape(len(rows), k, 4)
+        n = a.shape[0]
+        out = np.zeros((n, 8), dtype=np.uint64)
+        ctx._check(self.lib.zk_vk_input_sums(ctx.ptr, self.ptr, a.ctypes.data_as(_lib.u64p) if a.size else None, a.shape[1], n,
+                                             1 if tables else 0, out.ctypes.data_as(_lib.u64p)))
+        return out

@@ -50,6 +50,10 @@ class CrsOut(C.Structure):
                 ("beta_g2", u64p), ("gamma_g2", u64p), ("delta_g2", u64p), ("xi_g2", u64p)]
 
 
+class VkDesc(C.Structure):
+    _fields_ = [("input", C.c_size_t), ("alpha_g1", u64p), ("beta_g2", u64p), ("gamma_g2", u64p), ("delta_g2", u64p), ("sum_gamma_g1", u64p)]
+
+
 class QapCheckResult(C.Structure):
     _fields_ = [("bad_gates", C.c_uint32), ("first_bad", C.c_uint32), ("flags", C.c_uint32)]
 
@@ -186,6 +190,20 @@ SIGNATURES = {
     "zk_verify_batch_compressed": (C.c_int, [C.c_void_p, C.c_void_p, u64p, C.c_size_t, u8p, C.c_size_t, C.POINTER(C.c_int)]),
     "zk_verify_batch_all": (C.c_int, [C.c_void_p, C.c_void_p, u64p, C.c_size_t, u8p, C.c_size_t, u64p, C.POINTER(C.c_int)]),
     "zk_pairing": (C.c_int, [u64p, u64p, u64p]),
+    "zk_vk_create": (C.c_int, [C.POINTER(VkDesc), C.POINTER(C.c_void_p)]),
+    "zk_vk_from_crs": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "zk_vk_free": (None, [C.c_void_p]),
+    "zk_vk_dims": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t)]),
+    "zk_vk_bytes": (C.c_size_t, [C.c_size_t]),
+    "zk_vk_to_bytes": (C.c_int, [C.c_void_p, u8p, C.c_size_t]),
+    "zk_vk_from_bytes": (C.c_int, [u8p, C.c_size_t, C.POINTER(C.c_void_p)]),
+    "zk_vk_save": (C.c_int, [C.c_void_p, C.c_char_p]),
+    "zk_vk_load": (C.c_int, [C.c_char_p, C.POINTER(C.c_void_p)]),
+    "zk_vk_verify": (C.c_int, [C.c_void_p, u64p, C.c_size_t, u8p, C.POINTER(C.c_int)]),
+    "zk_vk_verify_batch": (C.c_int, [C.c_void_p, C.c_void_p, u64p, C.c_size_t, u8p, C.c_size_t, C.POINTER(C.c_int)]),
+    "zk_vk_verify_batch_compressed": (C.c_int, [C.c_void_p, C.c_void_p, u64p, C.c_size_t, u8p, C.c_size_t, C.POINTER(C.c_int)]),
+    "zk_vk_verify_batch_all": (C.c_int, [C.c_void_p, C.c_void_p, u64p, C.c_size_t, u8p, C.c_size_t, u64p, C.POINTER(C.c_int)]),
+    "zk_vk_input_sums": (C.c_int, [C.c_void_p, C.c_void_p, u64p, C.c_size_t, C.c_size_t, C.c_int, u64p]),
     "zk_profile_reset": (C.c_int, [C.c_void_p]),
     "zk_profile_count": (C.c_int, [C.c_void_p]),
     "zk_profile_entry": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),

@@ -140,6 +140,7 @@ static long* option_slot(zk_ctx* ctx, const char* key) {
     if (!std::strcmp(key, "basis_tree_min")) return &ctx->opt_basis_tree_min;
     if (!std::strcmp(key, "merge_lh")) return &ctx->opt_merge_lh;
     if (!std::strcmp(key, "witgen_scratch_kib")) return &ctx->opt_witgen_scratch_kib;
+    if (!std::strcmp(key, "vk_table_kib")) return &ctx->opt_vk_table_kib;
     if (!std::strcmp(key, "qap_check_chunk")) return &ctx->opt_qap_check_chunk;
     if (!std::strcmp(key, "qap_check_by_instance")) return &ctx->opt_qap_check_by_instance;
 #ifdef ZK_MEASURE

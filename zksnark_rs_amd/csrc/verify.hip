@@ -11,6 +11,7 @@
 //   e(alpha,beta) e(S,gamma) e(C,delta) == e(A,B)  <=>  FE(ml(alpha,beta) ml(S,gamma) ml(C,delta) ml(-A,B)) == 1.
 #include "pipeline.hpp"
 #include "pairing.cuh"
+#include "verify_host.hpp"
 
 namespace zk {
 
@@ -91,22 +92,8 @@ int zk_verify(zk_ctx* ctx, const zk_crs* crs, const uint64_t* inputs, size_t n_i
         G1A alpha, A, C;
         G2A beta, gamma, delta, B;
         ZK_REQUIRE(rd_g1(a1.data(), alpha) && rd_g2(b2.data(), beta) && rd_g2(g2.data(), gamma) && rd_g2(d2.data(), delta), ZK_ERR_ARG, "verify: CRS point not on the curve or outside G2");
-        if (!dec_g1(proof, A) || !dec_g2(proof + 65, B) || !dec_g1(proof + 194, C)) return;   // malformed / off-curve proof: rejected
-        // sum_term = sum_{i<=l} (1, inputs...)_i * sum_gamma_i  (zip truncates, mod.rs:308-314)
-        G1J sum = G1J::infinity();
-        for (size_t i = 0; i <= l && i < n_inputs + 1; ++i) {
-            G1A g;
-            ZK_REQUIRE(rd_g1(sg.data() + 8 * i, g), ZK_ERR_ARG, "verify: CRS point not on the curve");
-            Fr k;
-            if (i == 0) { k = Fr::zero(); k.l[0] = 1; }
-            else {
-                k = Fr::zero();
-                for (int w = 0; w < 4; ++w) { k.l[2 * w] = (uint32_t)inputs[4 * (i - 1) + w]; k.l[2 * w + 1] = (uint32_t)(inputs[4 * (i - 1) + w] >> 32); }
-                ZK_REQUIRE(k.raw_in_range(), ZK_ERR_RANGE, "verify: input >= r");
-            }
-            sum = jac_add(sum, jac_mul_words(G1J::from_affine(g), k.l));
-        }
-        G1A S = jac_to_affine(sum);
+        G1A S;
+        if (!verify_decode_sum(sg.data(), l, inputs, n_inputs, proof, A, B, C, S)) return;   // malformed / off-curve proof: rejected
         Fq12 f = miller_loop(alpha, beta) * miller_loop(S, gamma) * miller_loop(C, delta) * miller_loop(A.neg(), B);
         *ok = final_exponentiation(f) == Fq12::one() ? 1 : 0;
     });

@@ -99,8 +99,81 @@ __global__ void __launch_bounds__(VB_BLOCK) k_vb_final(const Fq12* F, const int*
 
 using namespace zk;
 
-// the body of zk_verify_batch and zk_verify_batch_compressed: `proofs` holds n_proofs strings of 259 bytes, or of 128 when
-// `compressed`; a chunk of the latter is uploaded as it is and decompressed into d_proofs on the device.  The error rules of the
+void zk::vb_launch_inputs(const uint64_t* d_x, size_t k, const G1A* d_sg, size_t m, G1A* d_S, hipStream_t s) {
+    hipLaunchKernelGGL(k_vb_inputs, dim3(ceil_div(m, VB_BLOCK)), dim3(VB_BLOCK), 0, s, d_x, k, d_sg, m, d_S);
+    ZK_HIP(hipGetLastError());
+}
+
+// the chunks of zk_verify_batch and zk_verify_batch_compressed over the verification constants: `proofs` holds n_proofs strings of
+// 259 bytes, or of 128 when `compressed`; a chunk of the latter is uploaded as it is and decompressed into d_proofs on the device.
+void zk::verify_batch_run(zk_ctx* ctx, const VerifyConsts& vc, const uint64_t* inputs, size_t n_inputs, const uint8_t* proofs,
+                          size_t n_proofs, int* ok, bool compressed) {
+    VerifyBatchState& st = vb_state(ctx);
+    hipStream_t s = st.stream;
+    const size_t k = std::min(vc.l, n_inputs);
+    const bool resident = vc.d_lines != nullptr;
+
+    // one arena: the constants unless they are resident, then the per-proof arrays of one chunk
+    const size_t m_max = std::min(n_proofs, (size_t)ZK_VERIFY_BATCH_CHUNK);
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t o_lines = 0, o_c = o_lines + (resident ? 0 : up(2 * ATE_LINES * sizeof(Line))), o_proofs = o_c + (resident ? 0 : up(sizeof(Fq12)));
+    const size_t o_x = o_proofs + up(m_max * ZK_PROOF_BYTES), o_A = o_x + up(m_max * k * 32), o_B = o_A + up(m_max * sizeof(G1A));
+    const size_t o_C = o_B + up(m_max * sizeof(G2A)), o_S = o_C + up(m_max * sizeof(G1A)), o_F = o_S + up(m_max * sizeof(G1A));
+    const size_t o_dec = o_F + up(m_max * sizeof(Fq12)), o_ok = o_dec + up(m_max * sizeof(int));
+    // the 128-byte strings of a chunk, behind everything zk_verify_batch itself lays out
+    const size_t o_cin = o_ok + up(m_max * sizeof(int)), total = o_cin + (compressed ? up(m_max * ZK_PROOF_COMPRESSED_BYTES) : 0);
+    if (st.arena.n < total) {
+        if (st.arena.p) st.retired.push_back(std::move(st.arena));
+        st.arena.alloc(total);
+    }
+    uint8_t* base = st.arena.p;
+    const Line* d_lines = resident ? vc.d_lines : (const Line*)(base + o_lines);
+    const Fq12* d_c = resident ? vc.d_c : (const Fq12*)(base + o_c);
+    uint8_t* d_proofs = base + o_proofs;
+    uint64_t* d_x = (uint64_t*)(base + o_x);
+    G1A *d_A = (G1A*)(base + o_A), *d_C = (G1A*)(base + o_C), *d_S = (G1A*)(base + o_S);
+    G2A* d_B = (G2A*)(base + o_B);
+    Fq12* d_F = (Fq12*)(base + o_F);
+    int *d_dec = (int*)(base + o_dec), *d_ok = (int*)(base + o_ok);
+    if (!resident) {
+        ZK_HIP(hipMemcpyAsync(base + o_lines, vc.h_lines, 2 * ATE_LINES * sizeof(Line), hipMemcpyHostToDevice, s));
+        ZK_HIP(hipMemcpyAsync(base + o_c, vc.h_c, sizeof(Fq12), hipMemcpyHostToDevice, s));
+    }
+
+    std::vector<uint64_t> packed;
+    for (size_t j0 = 0; j0 < n_proofs; j0 += m_max) {
+        const size_t m = std::min(m_max, n_proofs - j0);
+        const unsigned grid = ceil_div(m, VB_BLOCK);
+        if (compressed) {
+            uint8_t* d_cin = base + o_cin;
+            ZK_HIP(hipMemcpyAsync(d_cin, proofs + j0 * ZK_PROOF_COMPRESSED_BYTES, m * ZK_PROOF_COMPRESSED_BYTES, hipMemcpyHostToDevice, s));
+            pc_launch_decompress(d_cin, m, d_proofs, s);
+        } else {
+            ZK_HIP(hipMemcpyAsync(d_proofs, proofs + j0 * ZK_PROOF_BYTES, m * ZK_PROOF_BYTES, hipMemcpyHostToDevice, s));
+        }
+        if (k) {
+            const uint64_t* src = inputs + j0 * n_inputs * 4;
+            if (k != n_inputs) {   // only the first k inputs of a row are read (zip truncation)
+                packed.resize(m * k * 4);
+                for (size_t j = 0; j < m; ++j) std::memcpy(&packed[j * k * 4], src + j * n_inputs * 4, k * 32);
+                src = packed.data();
+            }
+            ZK_HIP(hipMemcpyAsync(d_x, src, m * k * 32, hipMemcpyHostToDevice, s));
+        }
+        hipLaunchKernelGGL(k_vb_decode, dim3(grid), dim3(VB_BLOCK), 0, s, d_proofs, m, d_A, d_B, d_C, d_dec);
+        ZK_HIP(hipGetLastError());
+        if (vc.d_tab) vk_launch_inputs(d_x, k, vc.d_sg, vc.d_tab, m, d_S, s);
+        else vb_launch_inputs(d_x, k, vc.d_sg, m, d_S, s);
+        hipLaunchKernelGGL(k_vb_miller, dim3(grid), dim3(VB_BLOCK), 0, s, d_S, d_A, d_B, d_C, m, d_lines, d_c, d_F);
+        ZK_HIP(hipGetLastError());
+        hipLaunchKernelGGL(k_vb_final, dim3(grid), dim3(VB_BLOCK), 0, s, d_F, d_dec, m, d_ok);
+        ZK_HIP(hipGetLastError());
+        ZK_HIP(hipMemcpyAsync(ok + j0, d_ok, m * sizeof(int), hipMemcpyDeviceToHost, s));
+        ZK_HIP(hipStreamSynchronize(s));   // also keeps `packed` and the arena's chunk arrays free for the next chunk
+    }
+}
+
+// the body of zk_verify_batch and zk_verify_batch_compressed: the constants of a CRS, made per call.  The error rules of the
 // compressed call are zk_verify_batch's exactly, texts included: its zk_last_error also reads "verify_batch: ...", on purpose.
 static int verify_batch_impl(zk_ctx* ctx, const zk_crs* crs, const uint64_t* inputs, size_t n_inputs, const uint8_t* proofs,
                              size_t n_proofs, int* ok, bool compressed) {
@@ -110,18 +183,8 @@ static int verify_batch_impl(zk_ctx* ctx, const zk_crs* crs, const uint64_t* inp
     std::fill(ok, ok + n_proofs, 0);
     return guarded(ctx, [&] {
         const size_t l = crs->input, k = std::min(l, n_inputs);
-        // the inputs zk_verify reads, before anything is launched
-        for (size_t j = 0; j < n_proofs; ++j)
-            for (size_t i = 0; i < k; ++i) {
-                Fr x;
-                const uint64_t* w = inputs + (j * n_inputs + i) * 4;
-                for (int h = 0; h < 4; ++h) { x.l[2 * h] = (uint32_t)w[h]; x.l[2 * h + 1] = (uint32_t)(w[h] >> 32); }
-                ZK_REQUIRE(x.raw_in_range(), ZK_ERR_RANGE, "verify_batch: input >= r");
-            }
-        if (!ctx->verify_batch) ctx->verify_batch = std::make_shared<VerifyBatchState>();
-        VerifyBatchState& st = *ctx->verify_batch;
-        if (!st.stream) ZK_HIP(hipStreamCreateWithFlags(&st.stream, hipStreamNonBlocking));
-        hipStream_t s = st.stream;
+        vb_check_inputs(inputs, n_inputs, k, n_proofs, "verify_batch: input >= r");
+        hipStream_t s = vb_state(ctx).stream;
 
         // the CRS points verify reads, copied on this stream (not through crs_download, which runs on the proving stream)
         G1A h_alpha;
@@ -146,63 +209,12 @@ static int verify_batch_impl(zk_ctx* ctx, const zk_crs* crs, const uint64_t* inp
         ml_lines(gamma, h_lines.data());
         ml_lines(delta, h_lines.data() + ATE_LINES);
         const Fq12 h_c = ml_proj(alpha, beta);
-
-        // one arena: constants, then the per-proof arrays of one chunk
-        const size_t m_max = std::min(n_proofs, (size_t)ZK_VERIFY_BATCH_CHUNK);
-        auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-        const size_t o_lines = 0, o_c = o_lines + up(h_lines.size() * sizeof(Line)), o_proofs = o_c + up(sizeof(Fq12));
-        const size_t o_x = o_proofs + up(m_max * ZK_PROOF_BYTES), o_A = o_x + up(m_max * k * 32), o_B = o_A + up(m_max * sizeof(G1A));
-        const size_t o_C = o_B + up(m_max * sizeof(G2A)), o_S = o_C + up(m_max * sizeof(G1A)), o_F = o_S + up(m_max * sizeof(G1A));
-        const size_t o_dec = o_F + up(m_max * sizeof(Fq12)), o_ok = o_dec + up(m_max * sizeof(int));
-        // the 128-byte strings of a chunk, behind everything zk_verify_batch itself lays out
-        const size_t o_cin = o_ok + up(m_max * sizeof(int)), total = o_cin + (compressed ? up(m_max * ZK_PROOF_COMPRESSED_BYTES) : 0);
-        if (st.arena.n < total) {
-            if (st.arena.p) st.retired.push_back(std::move(st.arena));
-            st.arena.alloc(total);
-        }
-        uint8_t* base = st.arena.p;
-        Line* d_lines = (Line*)(base + o_lines);
-        Fq12* d_c = (Fq12*)(base + o_c);
-        uint8_t* d_proofs = base + o_proofs;
-        uint64_t* d_x = (uint64_t*)(base + o_x);
-        G1A *d_A = (G1A*)(base + o_A), *d_C = (G1A*)(base + o_C), *d_S = (G1A*)(base + o_S);
-        G2A* d_B = (G2A*)(base + o_B);
-        Fq12* d_F = (Fq12*)(base + o_F);
-        int *d_dec = (int*)(base + o_dec), *d_ok = (int*)(base + o_ok);
-        ZK_HIP(hipMemcpyAsync(d_lines, h_lines.data(), h_lines.size() * sizeof(Line), hipMemcpyHostToDevice, s));
-        ZK_HIP(hipMemcpyAsync(d_c, &h_c, sizeof(Fq12), hipMemcpyHostToDevice, s));
-
-        std::vector<uint64_t> packed;
-        for (size_t j0 = 0; j0 < n_proofs; j0 += m_max) {
-            const size_t m = std::min(m_max, n_proofs - j0);
-            const unsigned grid = ceil_div(m, VB_BLOCK);
-            if (compressed) {
-                uint8_t* d_cin = base + o_cin;
-                ZK_HIP(hipMemcpyAsync(d_cin, proofs + j0 * ZK_PROOF_COMPRESSED_BYTES, m * ZK_PROOF_COMPRESSED_BYTES, hipMemcpyHostToDevice, s));
-                pc_launch_decompress(d_cin, m, d_proofs, s);
-            } else {
-                ZK_HIP(hipMemcpyAsync(d_proofs, proofs + j0 * ZK_PROOF_BYTES, m * ZK_PROOF_BYTES, hipMemcpyHostToDevice, s));
-            }
-            if (k) {
-                const uint64_t* src = inputs + j0 * n_inputs * 4;
-                if (k != n_inputs) {   // only the first k inputs of a row are read (zip truncation)
-                    packed.resize(m * k * 4);
-                    for (size_t j = 0; j < m; ++j) std::memcpy(&packed[j * k * 4], src + j * n_inputs * 4, k * 32);
-                    src = packed.data();
-                }
-                ZK_HIP(hipMemcpyAsync(d_x, src, m * k * 32, hipMemcpyHostToDevice, s));
-            }
-            hipLaunchKernelGGL(k_vb_decode, dim3(grid), dim3(VB_BLOCK), 0, s, d_proofs, m, d_A, d_B, d_C, d_dec);
-            ZK_HIP(hipGetLastError());
-            hipLaunchKernelGGL(k_vb_inputs, dim3(grid), dim3(VB_BLOCK), 0, s, d_x, k, crs->sum_gamma1.p, m, d_S);
-            ZK_HIP(hipGetLastError());
-            hipLaunchKernelGGL(k_vb_miller, dim3(grid), dim3(VB_BLOCK), 0, s, d_S, d_A, d_B, d_C, m, d_lines, d_c, d_F);
-            ZK_HIP(hipGetLastError());
-            hipLaunchKernelGGL(k_vb_final, dim3(grid), dim3(VB_BLOCK), 0, s, d_F, d_dec, m, d_ok);
-            ZK_HIP(hipGetLastError());
-            ZK_HIP(hipMemcpyAsync(ok + j0, d_ok, m * sizeof(int), hipMemcpyDeviceToHost, s));
-            ZK_HIP(hipStreamSynchronize(s));   // also keeps `packed` and the arena's chunk arrays free for the next chunk
-        }
+        VerifyConsts vc;
+        vc.l = l;
+        vc.d_sg = crs->sum_gamma1.p;
+        vc.h_lines = h_lines.data();
+        vc.h_c = &h_c;
+        verify_batch_run(ctx, vc, inputs, n_inputs, proofs, n_proofs, ok, compressed);
     });
 }
 

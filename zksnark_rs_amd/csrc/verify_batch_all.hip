@@ -84,6 +84,99 @@ __global__ void __launch_bounds__(VBA_BLOCK) k_vba_finish(const VbaAcc* acc, con
 
 using namespace zk;
 
+// every z_j != 0 and the inputs zk_verify reads < r, before anything is launched; t_0 = sum z_j < n 2^128 < r (no reduction)
+void zk::vba_check(const uint64_t* z, const uint64_t* inputs, size_t n_inputs, size_t k, size_t n_proofs, uint64_t t0[4]) {
+    t0[0] = t0[1] = t0[2] = t0[3] = 0;
+    for (size_t j = 0; j < n_proofs; ++j) {
+        ZK_REQUIRE(z[2 * j] | z[2 * j + 1], ZK_ERR_ARG, "verify_batch_all: a multiplier z_j is 0");
+        unsigned __int128 s = (unsigned __int128)t0[0] + z[2 * j];
+        t0[0] = (uint64_t)s;
+        s = (unsigned __int128)t0[1] + z[2 * j + 1] + (uint64_t)(s >> 64);
+        t0[1] = (uint64_t)s;
+        t0[2] += (uint64_t)(s >> 64);
+    }
+    vb_check_inputs(inputs, n_inputs, k, n_proofs, "verify_batch_all: input >= r");
+}
+
+// zk_verify_batch_all over the verification constants (d_sg, alpha; fx: the lines of beta, gamma, delta)
+void zk::verify_batch_all_run(zk_ctx* ctx, const VerifyConsts& vc, VbaFixed& fx, const uint64_t t0[4], const uint64_t* inputs, size_t n_inputs,
+                              const uint8_t* proofs, size_t n_proofs, const uint64_t* z, int* ok) {
+    VerifyBatchState& st = vb_state(ctx);
+    hipStream_t s = st.stream;
+    const size_t k = std::min(vc.l, n_inputs);
+    // once per call: t_0 alpha, and t = (t_0, 0, ..., 0)
+    uint32_t t0w[8];
+    for (int h = 0; h < 4; ++h) { t0w[2 * h] = (uint32_t)t0[h]; t0w[2 * h + 1] = (uint32_t)(t0[h] >> 32); }
+    fx.t0_alpha = jac_to_affine(g1_mul_bits(vc.alpha, t0w, 256));
+    std::vector<Fr> h_t(k + 1, Fr::zero());
+    for (int h = 0; h < 8; ++h) h_t[0].l[h] = t0w[h];
+    const VbaAcc h_acc = vba_identity();
+
+    // one arena: the call's constants and accumulators, then the arrays of one chunk
+    const size_t m_max = std::min(n_proofs, (size_t)ZK_VERIFY_BATCH_CHUNK);
+    const size_t n_part = ceil_div(m_max, VBA_BLOCK), n_tiles = ceil_div(m_max, VBA_ROWS), n_ts = ceil_div(k + 1, VBA_BLOCK);
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t o_fx = 0, o_acc = o_fx + up(sizeof(VbaFixed)), o_t = o_acc + up(sizeof(VbaAcc)), o_ok = o_t + up((k + 1) * sizeof(Fr));
+    const size_t o_proofs = o_ok + up(sizeof(int)), o_z = o_proofs + up(m_max * ZK_PROOF_BYTES), o_x = o_z + up(m_max * 16);
+    const size_t o_lane = o_x + up(m_max * k * 32), o_part = o_lane + up(m_max * sizeof(VbaAcc)), o_zm = o_part + up(n_part * sizeof(VbaAcc));
+    const size_t o_cols = o_zm + up(m_max * sizeof(Fr)), o_tsa = o_cols + up(n_tiles * k * sizeof(Fr)), o_tsb = o_tsa + up(n_ts * sizeof(VbaAcc));
+    const size_t total = o_tsb + up(n_ts * sizeof(VbaAcc));
+    if (st.arena.n < total) {
+        if (st.arena.p) st.retired.push_back(std::move(st.arena));
+        st.arena.alloc(total);
+    }
+    uint8_t* base = st.arena.p;
+    VbaFixed* d_fx = (VbaFixed*)(base + o_fx);
+    VbaAcc *d_acc = (VbaAcc*)(base + o_acc), *d_lane = (VbaAcc*)(base + o_lane), *d_part = (VbaAcc*)(base + o_part);
+    VbaAcc *d_tsa = (VbaAcc*)(base + o_tsa), *d_tsb = (VbaAcc*)(base + o_tsb);
+    Fr *d_t = (Fr*)(base + o_t), *d_zm = (Fr*)(base + o_zm), *d_cols = (Fr*)(base + o_cols);
+    int* d_ok = (int*)(base + o_ok);
+    uint8_t* d_proofs = base + o_proofs;
+    uint64_t *d_z = (uint64_t*)(base + o_z), *d_x = (uint64_t*)(base + o_x);
+    ZK_HIP(hipMemcpyAsync(d_fx, &fx, sizeof(VbaFixed), hipMemcpyHostToDevice, s));
+    ZK_HIP(hipMemcpyAsync(d_acc, &h_acc, sizeof(VbaAcc), hipMemcpyHostToDevice, s));
+    ZK_HIP(hipMemcpyAsync(d_t, h_t.data(), (k + 1) * sizeof(Fr), hipMemcpyHostToDevice, s));
+
+    // n values at a, combined VBA_BLOCK at a time, ping-ponging with b, until one is left; returns where it is
+    auto reduce = [&](VbaAcc* a, VbaAcc* b, size_t n) {
+        while (n > 1) {
+            const unsigned g = ceil_div(n, VBA_BLOCK);
+            hipLaunchKernelGGL(k_vba_reduce, dim3(g), dim3(VBA_BLOCK), 0, s, a, n, b);
+            ZK_HIP(hipGetLastError());
+            std::swap(a, b);
+            n = g;
+        }
+        return a;
+    };
+    for (size_t j0 = 0; j0 < n_proofs; j0 += m_max) {
+        const size_t m = std::min(m_max, n_proofs - j0);
+        ZK_HIP(hipMemcpyAsync(d_proofs, proofs + j0 * ZK_PROOF_BYTES, m * ZK_PROOF_BYTES, hipMemcpyHostToDevice, s));
+        ZK_HIP(hipMemcpyAsync(d_z, z + 2 * j0, m * 16, hipMemcpyHostToDevice, s));
+        if (k)   // only the first k inputs of a row are read (zip truncation)
+            ZK_HIP(hipMemcpy2DAsync(d_x, k * 32, inputs + j0 * n_inputs * 4, n_inputs * 32, k * 32, m, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_vba_lane, dim3(ceil_div(m, VBA_BLOCK)), dim3(VBA_BLOCK), 0, s, d_proofs, d_z, m, d_lane, d_zm);
+        ZK_HIP(hipGetLastError());
+        const VbaAcc* r = reduce(d_lane, d_part, m);
+        hipLaunchKernelGGL(k_vba_fold, dim3(1), dim3(1), 0, s, d_acc, r);
+        ZK_HIP(hipGetLastError());
+        if (k) {
+            hipLaunchKernelGGL(k_vba_columns, dim3(ceil_div(m, VBA_ROWS), ceil_div(k, VBA_BLOCK)), dim3(VBA_BLOCK), 0, s, d_x, k, d_zm, m, d_cols);
+            ZK_HIP(hipGetLastError());
+            hipLaunchKernelGGL(k_vba_colsum, dim3(ceil_div(k, VBA_BLOCK)), dim3(VBA_BLOCK), 0, s, d_cols, (size_t)ceil_div(m, VBA_ROWS), k, d_t + 1);
+            ZK_HIP(hipGetLastError());
+        }
+    }
+    hipLaunchKernelGGL(k_vba_ts, dim3(n_ts), dim3(VBA_BLOCK), 0, s, d_t, k + 1, vc.d_sg, d_tsa);
+    ZK_HIP(hipGetLastError());
+    const VbaAcc* ts = reduce(d_tsa, d_tsb, n_ts);
+    hipLaunchKernelGGL(k_vba_finish, dim3(1), dim3(1), 0, s, d_acc, ts, d_fx, d_ok);
+    ZK_HIP(hipGetLastError());
+    int verdict = 0;
+    ZK_HIP(hipMemcpyAsync(&verdict, d_ok, sizeof(int), hipMemcpyDeviceToHost, s));
+    ZK_HIP(hipStreamSynchronize(s));
+    *ok = verdict;
+}
+
 extern "C" int zk_verify_batch_all(zk_ctx* ctx, const zk_crs* crs, const uint64_t* inputs, size_t n_inputs, const uint8_t* proofs,
                                    size_t n_proofs, const uint64_t* z, int* ok) {
     if (!ctx || !crs || !proofs || !z || !ok || (n_inputs && !inputs)) return ZK_ERR_ARG;
@@ -94,27 +187,9 @@ extern "C" int zk_verify_batch_all(zk_ctx* ctx, const zk_crs* crs, const uint64_
     }
     return guarded(ctx, [&] {
         const size_t l = crs->input, k = std::min(l, n_inputs);
-        // before anything is launched: every z_j != 0, the inputs zk_verify reads < r; t_0 = sum z_j < n 2^128 < r (no reduction)
-        uint64_t t0[4] = {0, 0, 0, 0};
-        for (size_t j = 0; j < n_proofs; ++j) {
-            ZK_REQUIRE(z[2 * j] | z[2 * j + 1], ZK_ERR_ARG, "verify_batch_all: a multiplier z_j is 0");
-            unsigned __int128 s = (unsigned __int128)t0[0] + z[2 * j];
-            t0[0] = (uint64_t)s;
-            s = (unsigned __int128)t0[1] + z[2 * j + 1] + (uint64_t)(s >> 64);
-            t0[1] = (uint64_t)s;
-            t0[2] += (uint64_t)(s >> 64);
-        }
-        for (size_t j = 0; j < n_proofs; ++j)
-            for (size_t i = 0; i < k; ++i) {
-                Fr x;
-                const uint64_t* w = inputs + (j * n_inputs + i) * 4;
-                for (int h = 0; h < 4; ++h) { x.l[2 * h] = (uint32_t)w[h]; x.l[2 * h + 1] = (uint32_t)(w[h] >> 32); }
-                ZK_REQUIRE(x.raw_in_range(), ZK_ERR_RANGE, "verify_batch_all: input >= r");
-            }
-        if (!ctx->verify_batch) ctx->verify_batch = std::make_shared<VerifyBatchState>();
-        VerifyBatchState& st = *ctx->verify_batch;
-        if (!st.stream) ZK_HIP(hipStreamCreateWithFlags(&st.stream, hipStreamNonBlocking));
-        hipStream_t s = st.stream;
+        uint64_t t0[4];
+        vba_check(z, inputs, n_inputs, k, n_proofs, t0);
+        hipStream_t s = vb_state(ctx).stream;
 
         // the CRS points, copied on this stream and re-checked as zk_verify_batch does
         G1A h_alpha;
@@ -134,82 +209,17 @@ extern "C" int zk_verify_batch_all(zk_ctx* ctx, const zk_crs* crs, const uint64_
             G1A g;
             ZK_REQUIRE(check_g1(h_sg[i], g), ZK_ERR_ARG, "verify_batch_all: CRS point not on the curve");
         }
-        // once per call: the lines of beta, gamma and delta, t_0 alpha, and t = (t_0, 0, ..., 0)
+        // once per call: the lines of beta, gamma and delta
         auto h_fx = std::make_unique<VbaFixed>();
         const G2A* qs[3] = {&beta, &gamma, &delta};
         for (int q = 0; q < 3; ++q) {
             ml_lines(*qs[q], h_fx->lines[q]);
             h_fx->finite[q] = qs[q]->is_inf() ? 0 : 1;
         }
-        uint32_t t0w[8];
-        for (int h = 0; h < 4; ++h) { t0w[2 * h] = (uint32_t)t0[h]; t0w[2 * h + 1] = (uint32_t)(t0[h] >> 32); }
-        h_fx->t0_alpha = jac_to_affine(g1_mul_bits(alpha, t0w, 256));
-        std::vector<Fr> h_t(k + 1, Fr::zero());
-        for (int h = 0; h < 8; ++h) h_t[0].l[h] = t0w[h];
-        const VbaAcc h_acc = vba_identity();
-
-        // one arena: the call's constants and accumulators, then the arrays of one chunk
-        const size_t m_max = std::min(n_proofs, (size_t)ZK_VERIFY_BATCH_CHUNK);
-        const size_t n_part = ceil_div(m_max, VBA_BLOCK), n_tiles = ceil_div(m_max, VBA_ROWS), n_ts = ceil_div(k + 1, VBA_BLOCK);
-        auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-        const size_t o_fx = 0, o_acc = o_fx + up(sizeof(VbaFixed)), o_t = o_acc + up(sizeof(VbaAcc)), o_ok = o_t + up((k + 1) * sizeof(Fr));
-        const size_t o_proofs = o_ok + up(sizeof(int)), o_z = o_proofs + up(m_max * ZK_PROOF_BYTES), o_x = o_z + up(m_max * 16);
-        const size_t o_lane = o_x + up(m_max * k * 32), o_part = o_lane + up(m_max * sizeof(VbaAcc)), o_zm = o_part + up(n_part * sizeof(VbaAcc));
-        const size_t o_cols = o_zm + up(m_max * sizeof(Fr)), o_tsa = o_cols + up(n_tiles * k * sizeof(Fr)), o_tsb = o_tsa + up(n_ts * sizeof(VbaAcc));
-        const size_t total = o_tsb + up(n_ts * sizeof(VbaAcc));
-        if (st.arena.n < total) {
-            if (st.arena.p) st.retired.push_back(std::move(st.arena));
-            st.arena.alloc(total);
-        }
-        uint8_t* base = st.arena.p;
-        VbaFixed* d_fx = (VbaFixed*)(base + o_fx);
-        VbaAcc *d_acc = (VbaAcc*)(base + o_acc), *d_lane = (VbaAcc*)(base + o_lane), *d_part = (VbaAcc*)(base + o_part);
-        VbaAcc *d_tsa = (VbaAcc*)(base + o_tsa), *d_tsb = (VbaAcc*)(base + o_tsb);
-        Fr *d_t = (Fr*)(base + o_t), *d_zm = (Fr*)(base + o_zm), *d_cols = (Fr*)(base + o_cols);
-        int* d_ok = (int*)(base + o_ok);
-        uint8_t* d_proofs = base + o_proofs;
-        uint64_t *d_z = (uint64_t*)(base + o_z), *d_x = (uint64_t*)(base + o_x);
-        ZK_HIP(hipMemcpyAsync(d_fx, h_fx.get(), sizeof(VbaFixed), hipMemcpyHostToDevice, s));
-        ZK_HIP(hipMemcpyAsync(d_acc, &h_acc, sizeof(VbaAcc), hipMemcpyHostToDevice, s));
-        ZK_HIP(hipMemcpyAsync(d_t, h_t.data(), (k + 1) * sizeof(Fr), hipMemcpyHostToDevice, s));
-
-        // n values at a, combined VBA_BLOCK at a time, ping-ponging with b, until one is left; returns where it is
-        auto reduce = [&](VbaAcc* a, VbaAcc* b, size_t n) {
-            while (n > 1) {
-                const unsigned g = ceil_div(n, VBA_BLOCK);
-                hipLaunchKernelGGL(k_vba_reduce, dim3(g), dim3(VBA_BLOCK), 0, s, a, n, b);
-                ZK_HIP(hipGetLastError());
-                std::swap(a, b);
-                n = g;
-            }
-            return a;
-        };
-        for (size_t j0 = 0; j0 < n_proofs; j0 += m_max) {
-            const size_t m = std::min(m_max, n_proofs - j0);
-            ZK_HIP(hipMemcpyAsync(d_proofs, proofs + j0 * ZK_PROOF_BYTES, m * ZK_PROOF_BYTES, hipMemcpyHostToDevice, s));
-            ZK_HIP(hipMemcpyAsync(d_z, z + 2 * j0, m * 16, hipMemcpyHostToDevice, s));
-            if (k)   // only the first k inputs of a row are read (zip truncation)
-                ZK_HIP(hipMemcpy2DAsync(d_x, k * 32, inputs + j0 * n_inputs * 4, n_inputs * 32, k * 32, m, hipMemcpyHostToDevice, s));
-            hipLaunchKernelGGL(k_vba_lane, dim3(ceil_div(m, VBA_BLOCK)), dim3(VBA_BLOCK), 0, s, d_proofs, d_z, m, d_lane, d_zm);
-            ZK_HIP(hipGetLastError());
-            const VbaAcc* r = reduce(d_lane, d_part, m);
-            hipLaunchKernelGGL(k_vba_fold, dim3(1), dim3(1), 0, s, d_acc, r);
-            ZK_HIP(hipGetLastError());
-            if (k) {
-                hipLaunchKernelGGL(k_vba_columns, dim3(ceil_div(m, VBA_ROWS), ceil_div(k, VBA_BLOCK)), dim3(VBA_BLOCK), 0, s, d_x, k, d_zm, m, d_cols);
-                ZK_HIP(hipGetLastError());
-                hipLaunchKernelGGL(k_vba_colsum, dim3(ceil_div(k, VBA_BLOCK)), dim3(VBA_BLOCK), 0, s, d_cols, (size_t)ceil_div(m, VBA_ROWS), k, d_t + 1);
-                ZK_HIP(hipGetLastError());
-            }
-        }
-        hipLaunchKernelGGL(k_vba_ts, dim3(n_ts), dim3(VBA_BLOCK), 0, s, d_t, k + 1, crs->sum_gamma1.p, d_tsa);
-        ZK_HIP(hipGetLastError());
-        const VbaAcc* ts = reduce(d_tsa, d_tsb, n_ts);
-        hipLaunchKernelGGL(k_vba_finish, dim3(1), dim3(1), 0, s, d_acc, ts, d_fx, d_ok);
-        ZK_HIP(hipGetLastError());
-        int verdict = 0;
-        ZK_HIP(hipMemcpyAsync(&verdict, d_ok, sizeof(int), hipMemcpyDeviceToHost, s));
-        ZK_HIP(hipStreamSynchronize(s));
-        *ok = verdict;
+        VerifyConsts vc;
+        vc.l = l;
+        vc.d_sg = crs->sum_gamma1.p;
+        vc.alpha = alpha;
+        verify_batch_all_run(ctx, vc, *h_fx, t0, inputs, n_inputs, proofs, n_proofs, z, ok);
     });
 }

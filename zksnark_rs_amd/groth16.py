@@ -9,7 +9,7 @@
 """
 import os
 
-from . import R_MODULUS, ints_to_limbs
+from . import R_MODULUS, VerifyingKey, ints_to_limbs
 from . import proof_compress as _proof_compress, proof_decompress as _proof_decompress
 from .circuit import Circuit
 
@@ -87,19 +87,40 @@ def first_unsatisfied(qap, weights):
     return qap.ctx.qap_check(qap.handle, weights)[1]
 
 
+def verifying_key(sigma):
+    """The VerifyingKey of a CRS: alpha, beta, gamma, delta and sum_gamma, all verify reads.  It serialises (to_bytes / save) and
+    verifies single proofs on the host with no GPU; verify* below take it where they take `sigma`.  The batch calls run on the
+    key's `ctx` (VerifyingKey.ctx), here the CRS's context; restore a key with VerifyingKey.from_bytes(data, ctx=...) / load(path,
+    ctx=...) to use it with them."""
+    sigmag1, sigmag2 = sigma
+    return sigmag1.ctx.verifying_key(sigmag1.crs)
+
+
+def _key_ctx(vk):
+    if vk.ctx is None:
+        raise ValueError("groth16: this VerifyingKey has no Context (VerifyingKey.from_bytes(data, ctx=...), or assign key.ctx)")
+    return vk.ctx
+
+
 def verify(sigma, inputs, proof):
+    if isinstance(sigma, VerifyingKey):
+        return sigma.verify(inputs, proof)
     sigmag1, sigmag2 = sigma
     return sigmag1.ctx.verify(sigmag1.crs, inputs, proof)
 
 
 def verify_batch(sigma, inputs, proofs):
     """verify for many proofs over one CRS on the GPU: inputs[j] (the same count for every j) against proofs[j] -> bool array"""
+    if isinstance(sigma, VerifyingKey):
+        return sigma.verify_batch(_key_ctx(sigma), inputs, proofs)
     sigmag1, sigmag2 = sigma
     return sigmag1.ctx.verify_batch(sigmag1.crs, inputs, proofs)
 
 
 def verify_batch_compressed(sigma, inputs, proofs):
     """verify_batch over compressed 128-byte proofs (compress), decompressed on the GPU -> bool array"""
+    if isinstance(sigma, VerifyingKey):
+        return sigma.verify_batch_compressed(_key_ctx(sigma), inputs, proofs)
     sigmag1, sigmag2 = sigma
     return sigmag1.ctx.verify_batch_compressed(sigmag1.crs, inputs, proofs)
 
@@ -117,6 +138,8 @@ def decompress(compressed):
 def verify_batch_all(sigma, inputs, proofs):
     """one verdict for many proofs over one CRS on the GPU: True iff verify would accept every proof (random linear
     combination with secret multipliers drawn from os.urandom; a false pass has probability <= 1 / (2^128 - 1))"""
+    if isinstance(sigma, VerifyingKey):
+        return sigma.verify_batch_all(_key_ctx(sigma), inputs, proofs)
     sigmag1, sigmag2 = sigma
     return sigmag1.ctx.verify_batch_all(sigmag1.crs, inputs, proofs)
 
