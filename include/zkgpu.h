@@ -190,7 +190,10 @@ int zk_qap_upload_sparse_roots(zk_ctx* ctx, const zk_qap_sparse_desc* desc, cons
 
 /* Dense coefficient form, exactly the fields of QAP<CoefficientPoly<FrLocal>>: u, v, w are
  * m x n row-major (coefficient k of wire i at [i*n + k], zero padded), t has n+1 coefficients
- * (any roots; e.g. ASTParser's 1..n, circuit/mod.rs:517). */
+ * (any roots; e.g. ASTParser's 1..n, circuit/mod.rs:517) and is expected to have degree exactly n: t[n] != 0, monic or not.  The
+ * CRS of this library has n powers of x and n - 1 of x^i t(x), where the reference sizes them by deg t (groth16/mod.rs:134-197), so
+ * only for deg t = n are the proof bytes pinned to the reference's (tests/test_gpu_quotient.py); what a t of lower degree gives is
+ * not part of the contract. */
 int zk_qap_upload_dense(zk_ctx* ctx, const uint64_t* u, const uint64_t* v, const uint64_t* w, const uint64_t* t,
                         size_t m, size_t n, size_t input, zk_qap** out);
 void zk_qap_free(zk_qap* qap);

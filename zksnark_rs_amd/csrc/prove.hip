@@ -375,7 +375,7 @@ static int prove_form(zk_ctx* ctx, zk_crs& crs, const zk_qap& q) {
         if (tree || q.n <= basis_max_n()) crs_lagrange_from_powers(ctx, crs, q);
         else { arb_attach_integer_roots(ctx, const_cast<zk_qap&>(q)); form = 2; }
     }
-    if (form >= 2 && !q.t_is_zero && 2 * q.n - 1 > q.t_degree && 2 * q.n - 1 - q.t_degree >= 512 && !ctx->opt_long_division) {
+    if (form >= 2 && !q.t_is_zero && 2 * q.n - 1 > q.t_degree && 2 * q.n - 1 - q.t_degree >= ZK_NEWTON_MIN_QUOTIENT && !ctx->opt_long_division) {
         unsigned lc0 = 1;
         while (((size_t)1 << lc0) < 2 * q.n) ++lc0;
         qap_ensure_tinv(ctx, const_cast<zk_qap&>(q), 2 * q.n - 1 - q.t_degree, lc0);
@@ -415,7 +415,7 @@ static void arb_scalar_stage(zk_ctx* ctx, ProveSlot& S, const zk_qap& q, const F
     ZK_HIP(hipMemsetAsync(S.prod_b.p, 0, nc * sizeof(Fr), st));
     const size_t len_r = 2 * n - 1, d = q.t_degree;                   // t is monic of degree n: n - 1 quotient coefficients
     if (len_r > d) {
-        if (len_r - d >= 512 && !ctx->opt_long_division) {
+        if (len_r - d >= ZK_NEWTON_MIN_QUOTIENT && !ctx->opt_long_division) {
             S.div_work.ensure(nc);
             poly_divide_newton(ctx, q, S.prod_a.p, len_r, lc, S.div_work.p, S.prod_b.p);
         } else {
@@ -719,8 +719,8 @@ int prove_submit(zk_ctx* ctx, const zk_crs& crs_c, const zk_qap& qap_c, const Fr
         ZK_HIP(hipMemsetAsync(S.prod_b.p, 0, nc * sizeof(Fr), st));
         size_t len_r = 2 * n - 1, d = q.t_degree;
         if (len_r > d) {
-            // long division below 512 quotient coefficients (as the reference); above, the O(n log n) form
-            if (len_r - d >= 512 && !ctx->opt_long_division) {
+            // long division below ZK_NEWTON_MIN_QUOTIENT quotient coefficients (as the reference); from there on, the O(n log n) form
+            if (len_r - d >= ZK_NEWTON_MIN_QUOTIENT && !ctx->opt_long_division) {
                 S.div_work.ensure(nc);
                 poly_divide_newton(ctx, q, S.prod_a.p, len_r, lc, S.div_work.p, S.prod_b.p);
             } else {
