@@ -318,7 +318,18 @@ typedef struct {
 int zk_crs_upload(zk_ctx* ctx, const zk_crs_desc* desc, zk_crs** out);
 
 /* groth16::setup (groth16/mod.rs:134-197) on the GPU with the five random draws injected:
- * trapdoor = alpha | beta | gamma | delta | x (4 words each, all non-zero). */
+ * trapdoor = alpha | beta | gamma | delta | x (4 canonical words each).  Every element is non-zero and < r: a zero element gives
+ * ZK_ERR_DIV_BY_ZERO (Random for FrLocal never yields one, fr.rs:90-99), an element >= r ZK_ERR_RANGE; *out is NULL on every failure
+ * and the context and the QAP stay usable.
+ * x on a root of t:
+ *   - integer-roots form (zk_qap_upload_sparse_integers): x in 1..2n-1 -- the roots 1..n and the second node set n+1..2n-1 of the
+ *     Lagrange-basis H points -- gives ZK_ERR_UNSUPPORTED (draw another x); 2n and everything above is accepted;
+ *   - arbitrary-roots form (zk_qap_upload_sparse_roots): x equal to one of the roots gives ZK_ERR_UNSUPPORTED;
+ *     (the reference would emit a CRS in both cases: a deliberate deviation)
+ *   - roots-of-unity form (zk_qap_upload_sparse) and dense form: accepted, and the CRS is the reference's for that x: t(x) = 0, so
+ *     every xi_t_g1 point is infinity, and so is every sum_gamma / sum_delta point of a wire with no entry at the gate at x.  On
+ *     such a CRS zk_verify checks the gate at x only: a witness that fails any other gate proves and verifies.  Never use one
+ *     outside tests. */
 int zk_setup(zk_ctx* ctx, const zk_qap* qap, const uint64_t trapdoor[20], zk_crs** out);
 
 /* Copy a device CRS back into caller-provided host buffers (any pointer may be NULL = skip). */

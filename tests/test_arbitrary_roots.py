@@ -290,8 +290,9 @@ def test_arbitrary_roots_container_limits_and_errors(ctx, tmp_path):
     assert e.value.status == zk._lib.ZK_ERR_RANGE
     # the trapdoor's x on a root: refused like the reference's division by zero would be
     td_bad = td.copy(); td_bad[4] = roots[9]
-    with pytest.raises(zk.ZkError):
+    with pytest.raises(zk.ZkError) as e:
         ctx.setup(qap, td_bad)
+    assert e.value.status == zk._lib.ZK_ERR_UNSUPPORTED
     # a batch of one is a proof
     import torch
     d = torch.from_numpy(wts.view(np.int64)).cuda()
