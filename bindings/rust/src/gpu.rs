@@ -50,6 +50,10 @@ pub struct ZkSparseRows { ptr: *const u64, gate: *const u32, val: *const u64 }  
 pub struct ZkQapSparseDesc { log_n: c_uint, m: usize, input: usize, u: ZkSparseRows, v: ZkSparseRows, w: ZkSparseRows }
 #[repr(C)]
 pub struct ZkQapCheckResult { pub bad_gates: u32, pub first_bad: u32, pub flags: u32 }   // zk_qap_check_result (12 bytes)
+#[repr(C)]
+pub struct ZkCrsCheckResult { pub failed: u32, pub flags: u32 }   // zk_crs_check_result: ZK_CRS_CHECK_* bits
+pub const ZK_CRS_CHECK_T_ZERO: u32 = 1;                // flags: x is a root of t (consistent, unsound)
+pub const ZK_CRS_CHECK_LAGRANGE_PRESENT: u32 = 2;      // flags: the CRS carries Lagrange-basis arrays
 #[repr(C)] pub struct ZkVk { _p: [u8; 0] }
 #[repr(C)]
 pub struct ZkVkDesc {                                    // zk_vk_desc
@@ -123,6 +127,8 @@ extern "C" {
     fn zk_qap_check(ctx: *mut ZkCtx, qap: *const ZkQap, weights: *const u64, m: usize, out: *mut ZkQapCheckResult) -> c_int;
     fn zk_qap_check_dev(ctx: *mut ZkCtx, qap: *const ZkQap, d_weights: *const c_void, m: usize, stride: usize, count: usize,
                         out: *mut ZkQapCheckResult) -> c_int;
+    // is the CRS a Groth16 CRS of some trapdoor for this QAP?  challenge = null: drawn from the OS inside the library
+    fn zk_crs_check(ctx: *mut ZkCtx, crs: *const ZkCrs, qap: *const ZkQap, challenge: *const u64, out: *mut ZkCrsCheckResult) -> c_int;
     // a stream of proofs: witnesses in page-locked host memory, two tickets in flight
     fn zk_host_alloc(bytes: usize, out: *mut *mut c_void) -> c_int;
     fn zk_host_free(p: *mut c_void);
@@ -617,6 +623,19 @@ impl GpuProver {
     pub fn is_satisfied(&self, weights: &[FrLocal]) -> bool {
         let (bad, _, wire0_ok) = self.check_witness(weights);
         bad == 0 && wire0_ok
+    }
+    /// What the reference lacks as well: is the CRS this prover holds (set up here, uploaded, or read from a file) a Groth16 CRS of
+    /// SOME trapdoor for its QAP?  (zk_crs_check: the relations and their bits are in include/zkgpu.h.)  The challenge is drawn from
+    /// the OS inside the library -- whoever made the CRS must not be able to predict it.  -> (failed bits, flags); good means
+    /// failed == 0 and flags & ZK_CRS_CHECK_T_ZERO == 0, which is what `crs_is_good` returns.
+    pub fn check_crs(&self) -> (u32, u32) {
+        let mut res = ZkCrsCheckResult { failed: 0, flags: 0 };
+        unsafe { check(self.ctx.0, zk_crs_check(self.ctx.0, self.crs, self.qap, std::ptr::null(), &mut res)); }
+        (res.failed, res.flags)
+    }
+    pub fn crs_is_good(&self) -> bool {
+        let (failed, flags) = self.check_crs();
+        failed == 0 && flags & ZK_CRS_CHECK_T_ZERO == 0
     }
     /// the same for `count` witnesses resident on the device, m elements each, `stride` elements apart (zk_witgen_run's layout: stride == m)
     pub fn check_witnesses_dev(&self, d_weights: *const c_void, m: usize, stride: usize, count: usize) -> Vec<ZkQapCheckResult> {

@@ -341,7 +341,65 @@ int zk_crs_dims(const zk_crs* crs, size_t* n, size_t* m, size_t* input);
 int zk_crs_download(zk_ctx* ctx, const zk_crs* crs, const zk_crs_out* out);
 void zk_crs_free(zk_crs* crs);
 
-/* On-disk CRS container.  The reference has no serialisation of SigmaG1/SigmaG2
+/* Is this CRS a Groth16 CRS for THIS QAP?  zk_crs_upload and zk_crs_load take arrays from anywhere (a ceremony, the reference, a file,
+ * another machine) and check ranges, curves and the G2 subgroup only; a wrong sum_delta point, an xi_t array off by one power or the
+ * CRS of another circuit of the same dimensions still yields 259 well-formed bytes that zk_verify rejects.  This is the check a
+ * receiver of a CRS runs once, without the trapdoor (what bellman's phase-2 verify and `snarkjs zkey verify` do): a handful of inner
+ * products over the resident arrays and fewer than twenty pairings.
+ * Notation: G = xi_g1[0], H = xi_g2[0]; s = the challenge, 1 <= s < r; rho_k = s^k; t(X) = X t'(X) + t_0 (deg t' = n - 1; roots of
+ * unity: t' = X^(n-1), t_0 = -1); sums run over the CRS's own arrays.  A relation that does not hold sets its bit in out->failed:
+ *   GENERATORS   xi_g1[0] and xi_g2[0] are the bases zk_setup encrypts with (69 G1::one(), 96 G2::one(): fr.rs:106-113).
+ *   POWERS_G1    (n >= 2) P = sum_{k<=n-2} rho_k xi_g1[k], Q = sum_{k<=n-2} rho_k xi_g1[k+1]:  e(P, xi_g2[1]) = e(Q, H).
+ *   POWERS_G2    e(sum_{k<n} rho_k xi_g1[k], H) = e(G, sum_{k<n} rho_k xi_g2[k]).
+ *   TWINS        e(beta_g1, H) = e(G, beta_g2) and e(delta_g1, H) = e(G, delta_g2).
+ *   XI_T         (n >= 2) e(sum_{k<=n-2} rho_k xi_t_g1[k], delta_g2) = e(Q, [t'(x)]_2) e(t_0 P, H), [t'(x)]_2 = sum_j t'_j xi_g2[j]
+ *                (the CRS holds n powers, so [t(x)] itself cannot be formed in either group: hence the split of t).
+ *   WIRES        rho_i = s^i over ALL wires i < m; U = [sum_i rho_i u_i(x)]_1, V = [sum_i rho_i v_i(x)]_2, W = [sum_i rho_i w_i(x)]_1
+ *                formed from xi_g1 / xi_g2:  e(sum_{i<=l} rho_i sum_gamma_g1[i], gamma_g2) e(sum_{i>l} rho_i sum_delta_g1[i-l-1], delta_g2)
+ *                = e(U, beta_g2) e(alpha_g1, V) e(W, H).  One relation for both arrays; only when it fails it is repeated over the
+ *                wires i <= l alone and over the rest, and WIRES_GAMMA / WIRES_DELTA (or both) say which array to look at.
+ *   LAGRANGE     (only with ZK_CRS_CHECK_LAGRANGE_PRESENT) S_d(z) = sum_{k<d} (s z)^k:  sum_k S_n(k+1) lag1[k] = sum_{k<n} rho_k xi_g1[k],
+ *                the same for lag2 against xi_g2, and sum_j S_{n-1}(n+1+j) lagS_t1[j] = sum_{k<=n-2} rho_k xi_t_g1[k] -- point
+ *                equalities, no pairing (lag1, lag2, lagS_t1: the Lagrange-basis arrays zk_setup makes for an integer-roots QAP and a
+ *                ZKCRSv2 file carries).
+ *   DEGENERATE   gamma_g2, delta_g2, delta_g1, alpha_g1, beta_g1 or beta_g2 is the point at infinity.
+ * out->flags: ZK_CRS_CHECK_LAGRANGE_PRESENT, and ZK_CRS_CHECK_T_ZERO when xi_t_g1[0] is infinity: x is a root of t, every relation
+ * holds and the CRS is consistent but UNSOUND (see zk_setup).  "The CRS is good" means failed == 0 && !(flags & ZK_CRS_CHECK_T_ZERO).
+ * What a good CRS is: the CRS of SOME trapdoor (alpha, beta, gamma, delta, x) for this QAP.  x is known to nobody, so that is the whole
+ * claim; a CRS byte-equal to zk_setup's for any trapdoor passes for every challenge.
+ * Soundness: each relation is a polynomial identity in s of degree below max(n, m); one wrong entry makes the polynomial
+ * non-zero, so at most max(n, m) of the r values of s let it pass: error <= 2^23 / r -- for an s the maker of the CRS could NOT
+ * PREDICT.  Knowing s, two entries of one array can be altered so that they cancel (xi_t[0] += D, xi_t[1] -= D / s).  So, as for the
+ * z_j of zk_verify_batch_all: a fixed `challenge` is for tests; challenge = NULL draws 256 bits from the OS and reduces them mod r.
+ *  - All four QAP forms (zk_qap_kind 0..3) and every CRS however it arrived (zk_setup, zk_crs_upload, zk_crs_load of either version).
+ *  - Read-only on the CRS: the prover's window tables are neither built, used nor replaced and no Lagrange-basis array is attached; a
+ *    proof made before the check and one made after it are byte-equal.  On the QAP handle the first check builds what the first
+ *    zk_qap_check builds (W's rows by gate) and, for the integer-roots form, the interpolation tree of 1..n.
+ *  - Synchronous, on a stream of its own; an outstanding zk_prove_submit ticket is not disturbed (the one-off tables of the check are
+ *    freed before the call returns, which lets the device drain first).  Device memory: the window tables of the five arrays, about
+ *    what the prover's tables take.
+ *  - ZK_ERR_ARG: null ctx / crs / qap / out, a CRS whose (n, m, input) differ from the QAP's, a handle of another context,
+ *    challenge = 0.  ZK_ERR_RANGE: challenge >= r.  On every error *out is untouched. */
+#define ZK_CRS_CHECK_GENERATORS 0x001u
+#define ZK_CRS_CHECK_POWERS_G1 0x002u
+#define ZK_CRS_CHECK_POWERS_G2 0x004u
+#define ZK_CRS_CHECK_TWINS 0x008u
+#define ZK_CRS_CHECK_XI_T 0x010u
+#define ZK_CRS_CHECK_WIRES 0x020u
+#define ZK_CRS_CHECK_WIRES_GAMMA 0x040u
+#define ZK_CRS_CHECK_WIRES_DELTA 0x080u
+#define ZK_CRS_CHECK_LAGRANGE 0x100u
+#define ZK_CRS_CHECK_DEGENERATE 0x200u
+#define ZK_CRS_CHECK_T_ZERO 1u             /* flags */
+#define ZK_CRS_CHECK_LAGRANGE_PRESENT 2u   /* flags */
+typedef struct {
+    uint32_t failed;   /* ZK_CRS_CHECK_GENERATORS .. ZK_CRS_CHECK_DEGENERATE: the relations that do not hold */
+    uint32_t flags;    /* ZK_CRS_CHECK_T_ZERO | ZK_CRS_CHECK_LAGRANGE_PRESENT */
+} zk_crs_check_result;
+int zk_crs_check(zk_ctx* ctx, const zk_crs* crs, const zk_qap* qap, const uint64_t challenge[4] /* NULL = drawn from the OS */,
+                 zk_crs_check_result* out);
+
+/* On-disk CRS container. The reference has no serialisation of SigmaG1/SigmaG2
  * (groth16/mod.rs:105-121), and setup (mod.rs:134-197) draws a fresh trapdoor on every call, so a CRS must be
  * written down to be reused.  Format: "ZKCRSv1\0", n, m, input, FNV-1a-64 of the payload, then the arrays of
  * zk_crs_desc in declaration order as canonical little-endian words.  A CRS that zk_setup made for an integer-roots QAP

@@ -15,6 +15,7 @@
 //   groth16::prove(&qap, (&s1, &s2), &weights)  (mod.rs:213-296)   zksnark::groth16::prove(ctx, qap, sigma, weights)
 //   groth16::verify((s1, s2), &inputs, proof)   (mod.rs:299-320)   zksnark::groth16::verify(ctx, sigma, inputs, proof)
 //   (none: prove drops the remainder, mod.rs:277)                  zksnark::groth16::is_satisfied / which_is_unsatisfied(ctx, qap, weights)
+//   (none: a CRS is taken on trust)                                zksnark::groth16::check_setup(ctx, qap, sigma)
 //
 // Where the reference panics (division by zero fr.rs:54,69; "Dividend must be non-zero" field/mod.rs:440;
 // unwrap() of a ParseErr) this API throws zksnark::Error carrying the ABI status and message.  The
@@ -327,6 +328,26 @@ inline bool is_satisfied(const Context& c, const QAP& qap, const std::vector<FrL
 inline std::optional<size_t> which_is_unsatisfied(const Context& c, const QAP& qap, const std::vector<FrLocal>& weights_) {
     const zk_qap_check_result r = check(c, qap, weights_);
     return r.first_bad == ZK_QAP_CHECK_NONE ? std::nullopt : std::optional<size_t>(r.first_bad);
+}
+
+// What the reference lacks as well: is `sigma` a CRS of SOME trapdoor for this QAP (zk_crs_check)?  What a prover that did not run
+// setup itself asks once about the CRS it was handed (a ceremony, a file, another machine).  The challenge is drawn from the OS
+// inside the library; check_setup_with fixes it and is for tests -- whoever made the CRS must not be able to predict it.
+struct SetupCheck {
+    uint32_t failed = 0;   // ZK_CRS_CHECK_GENERATORS .. ZK_CRS_CHECK_DEGENERATE: the relations that do not hold
+    uint32_t flags = 0;    // ZK_CRS_CHECK_T_ZERO | ZK_CRS_CHECK_LAGRANGE_PRESENT
+    bool ok() const { return failed == 0 && !(flags & ZK_CRS_CHECK_T_ZERO); }
+    bool has(uint32_t bit) const { return (failed & bit) != 0; }
+};
+inline SetupCheck check_setup_with(const Context& c, const QAP& qap, const Sigma& sigma, const FrLocal& challenge) {
+    zk_crs_check_result r{};
+    c.check(zk_crs_check(c.get(), sigma.get(), qap.get(), challenge.w.data(), &r), "groth16::check_setup");
+    return SetupCheck{r.failed, r.flags};
+}
+inline SetupCheck check_setup(const Context& c, const QAP& qap, const Sigma& sigma) {
+    zk_crs_check_result r{};
+    c.check(zk_crs_check(c.get(), sigma.get(), qap.get(), nullptr, &r), "groth16::check_setup");
+    return SetupCheck{r.failed, r.flags};
 }
 
 // groth16::verify((sigma_g1, sigma_g2), &inputs, proof) (mod.rs:299-320)

@@ -25,7 +25,7 @@ Q_MODULUS = 21888242871839275222246405745257275088696311157297823662689037894645
 
 __all__ = ["Context", "ZkError", "fr_to_limbs", "limbs_to_int", "ints_to_limbs", "limbs_to_ints",
            "PROOF_BYTES", "PARTIAL_BYTES", "MAX_IN_FLIGHT", "MAX_BATCH", "R_MODULUS", "Q_MODULUS", "SplitMix64", "pairing", "proof_save", "proof_load",
-           "PROOF_COMPRESSED_BYTES", "proof_compress", "proof_decompress", "VerifyingKey"]
+           "PROOF_COMPRESSED_BYTES", "proof_compress", "proof_decompress", "VerifyingKey", "CrsCheck"]
 
 
 class ZkError(RuntimeError):
@@ -171,6 +171,40 @@ class Qap(_Handle):
 class Crs(_Handle):
     """Device-resident (SigmaG1, SigmaG2) (groth16/mod.rs:105-121)."""
     n = m = input = 0
+
+
+class CrsCheck:
+    """What zk_crs_check found: `failed` = the ZK_CRS_CHECK_* bits of the relations that do not hold, `flags` = T_ZERO |
+    LAGRANGE_PRESENT.  The bit values are class attributes (CrsCheck.WIRES, ...); `names` lists the failed ones; `ok` is "the CRS is
+    good": no relation fails and x is not a root of t."""
+    T_ZERO = _lib.CRS_CHECK_T_ZERO
+    LAGRANGE_PRESENT = _lib.CRS_CHECK_LAGRANGE_PRESENT
+
+    def __init__(self, failed, flags):
+        self.failed, self.flags = int(failed), int(flags)
+
+    @property
+    def ok(self):
+        return self.failed == 0 and not (self.flags & self.T_ZERO)
+
+    @property
+    def t_zero(self):
+        return bool(self.flags & self.T_ZERO)
+
+    @property
+    def lagrange_present(self):
+        return bool(self.flags & self.LAGRANGE_PRESENT)
+
+    @property
+    def names(self):
+        return [n for k, n in enumerate(_lib.CRS_CHECK_BITS) if self.failed >> k & 1]
+
+    def __repr__(self):
+        return "CrsCheck(failed=%s, t_zero=%s, lagrange_present=%s)" % ("|".join(self.names) or "0", self.t_zero, self.lagrange_present)
+
+
+for _k, _n in enumerate(_lib.CRS_CHECK_BITS):
+    setattr(CrsCheck, _n, 1 << _k)
 
 
 class Context:
@@ -372,6 +406,18 @@ class Context:
         c = Crs(self, p, self.lib.zk_crs_free)
         c.n, c.m, c.input = n, m, input
         return c
+
+    def crs_check(self, crs, qap, challenge=None):
+        """zk_crs_check: is `crs` a Groth16 CRS of some trapdoor for `qap`?  -> CrsCheck (.ok, .failed, .flags, .names).  challenge:
+        None draws it from the OS inside the library (the only sound choice: whoever made the CRS must not be able to predict it); an
+        int in [1, r) or (4,) limbs fixes it, for tests."""
+        if challenge is None:
+            sp = None
+        else:
+            s_, sp = _u64(fr_to_limbs(challenge) if isinstance(challenge, int) else np.asarray(challenge).reshape(4))
+        out = _lib.CrsCheckResult(0xFFFFFFFF, 0xFFFFFFFF)
+        self._check(self.lib.zk_crs_check(self.ptr, crs.ptr, qap.ptr, sp, C.byref(out)))
+        return CrsCheck(out.failed, out.flags)
 
     def qap_weighted_sum(self, qap, weights, which):
         """sum_i weights[i] * u_i / v_i / w_i (which = 0 / 1 / 2; mod.rs:233-253): coefficients (dense QAP) or values on the domain

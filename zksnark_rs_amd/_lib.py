@@ -21,6 +21,10 @@ MAX_BATCH = 64          # ZK_MAX_BATCH
 QAP_CHECK_NONE = 0xFFFFFFFF     # ZK_QAP_CHECK_NONE
 QAP_CHECK_WIRE0 = 1             # ZK_QAP_CHECK_WIRE0
 QAP_CHECK_CHUNK_LANES = 1 << 28  # ZK_QAP_CHECK_CHUNK_LANES
+# zk_crs_check_result.failed (ZK_CRS_CHECK_*), in bit order, and .flags
+CRS_CHECK_BITS = ("GENERATORS", "POWERS_G1", "POWERS_G2", "TWINS", "XI_T", "WIRES", "WIRES_GAMMA", "WIRES_DELTA", "LAGRANGE", "DEGENERATE")
+CRS_CHECK_T_ZERO = 1             # ZK_CRS_CHECK_T_ZERO
+CRS_CHECK_LAGRANGE_PRESENT = 2   # ZK_CRS_CHECK_LAGRANGE_PRESENT
 
 u64p = C.POINTER(C.c_uint64)
 u32p = C.POINTER(C.c_uint32)
@@ -56,6 +60,10 @@ class VkDesc(C.Structure):
 
 class QapCheckResult(C.Structure):
     _fields_ = [("bad_gates", C.c_uint32), ("first_bad", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class CrsCheckResult(C.Structure):
+    _fields_ = [("failed", C.c_uint32), ("flags", C.c_uint32)]
 
 
 # zk_comm_ops / zk_mgpu_backend: tables of C callbacks (tests plug gloo and CPU stand-ins in here)
@@ -129,6 +137,7 @@ SIGNATURES = {
     "zk_circuit_qap_sparse": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
     "zk_crs_upload": (C.c_int, [C.c_void_p, C.POINTER(CrsDesc), C.POINTER(C.c_void_p)]),
     "zk_setup": (C.c_int, [C.c_void_p, C.c_void_p, u64p, C.POINTER(C.c_void_p)]),
+    "zk_crs_check": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, u64p, C.POINTER(CrsCheckResult)]),
     "zk_crs_dims": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "zk_crs_download": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(CrsOut)]),
     "zk_crs_free": (None, [C.c_void_p]),

@@ -137,8 +137,8 @@ void crs_download(zk_ctx* ctx, const zk_crs& c, const zk_crs_out& o) {
 }
 
 // The Lagrange-basis arrays of an integer-roots CRS (aproots.hip) -- for the file container: host words <-> device.  They are
-// range- and curve-checked like every uploaded point; that they are the same CRS in another basis is the file's business (it is
-// the prover's own file, checksummed; a wrong array yields proofs that zk_verify rejects).
+// range- and curve-checked like every uploaded point; that they are the same CRS in another basis is not decided here but by
+// zk_crs_check (crs_check.hip, the LAGRANGE relation), as is everything else that ties the arrays of a CRS to each other.
 void crs_download_lagrange(zk_ctx* ctx, const zk_crs& c, uint64_t* lag1, uint64_t* lagS_t1, uint64_t* lag2) {
     ZK_REQUIRE(c.ap, ZK_ERR_ARG, "CRS holds no Lagrange-basis arrays");
     down_points(ctx, c.lag1, lag1, c.n);
@@ -347,6 +347,19 @@ static const G2GenWords G2GEN = {
     {0xaef312c2u, 0x97e485b7u, 0x35a9e712u, 0xf1aa4933u, 0x31fb5d25u, 0x7260bfb7u, 0x920d483au, 0x198e9393u},
     {0x66fa7daau, 0x4ce6cc01u, 0x0c43d37bu, 0xe3d1e769u, 0x8dcb408fu, 0x4aab7180u, 0xdb8c6debu, 0x12c85ea5u},
     {0xd122975bu, 0x55acdadcu, 0x70b38ef3u, 0xbc4b3133u, 0x690c3395u, 0xec9e99adu, 0x585ff075u, 0x090689d0u}};
+
+// 69 * G1::one() and 96 * G2::one() (fr.rs:106-113) on the host: what zk_crs_check compares xi_g1[0] and xi_g2[0] with
+void crs_generators(G1A* g1, G2A* g2) {
+    auto fq = [](const uint32_t* w) {
+        Fq x;
+        for (int i = 0; i < 8; ++i) x.l[i] = w[i];
+        return Fq::from_canonical(x);
+    };
+    const G1J one1{Fq::from_u32(1), Fq::from_u32(2), Fq::one()};
+    const G2J one2{Fq2{fq(G2GEN.x0), fq(G2GEN.x1)}, Fq2{fq(G2GEN.y0), fq(G2GEN.y1)}, Fq2::one()};
+    *g1 = jac_to_affine(jac_mul_small(one1, 69));
+    *g2 = jac_to_affine(jac_mul_small(one2, 96));
+}
 
 __device__ __forceinline__ Fq fq_from_words(const uint32_t* w) {
     Fq x;

@@ -129,6 +129,8 @@ void crs_ensure_rank_tables(zk_ctx*, zk_crs&, bool brev, unsigned log_n, bool la
 void crs_download_lagrange(zk_ctx*, const zk_crs&, uint64_t* lag1, uint64_t* lagS_t1, uint64_t* lag2);
 void crs_attach_lagrange(zk_ctx*, zk_crs&, const uint64_t* lag1, const uint64_t* lagS_t1, const uint64_t* lag2);
 void crs_ensure_fixed_tables(zk_ctx*, zk_crs&);
+void crs_generators(G1A* g1, G2A* g2);                             // crs.hip: the encryption bases of zk_setup (Montgomery form), host code
+void qc_ensure_w_gate(const zk_qap&, hipStream_t);                 // qap_check.hip: W's rows by gate, built once per handle (zk_qap_check*, zk_crs_check)
 size_t basis_max_n();                                              // the largest n crs_lagrange_from_powers takes
 void arb_attach_integer_roots(zk_ctx*, zk_qap&);                    // arbroots.hip: the tree of the roots 1..n for an integer-roots QAP (see prove.hip)
 void crs_lagrange_from_powers_tree(zk_ctx*, zk_crs&, const zk_qap&);   // gbasis.hip: the same arrays by the transposed interpolation tree, O(n log^2 n) point operations

@@ -124,7 +124,7 @@ __global__ void __launch_bounds__(QC_BLOCK) k_qap_check(QcCsr u, QcCsr v, QcCsr 
 }
 
 // w_wire (by wire, val R) -> w_gate (by gate, val R^2), once per handle
-static void qc_ensure_w_gate(const zk_qap& q, hipStream_t s) {
+void qc_ensure_w_gate(const zk_qap& q, hipStream_t s) {
     if (q.has_w_gate) return;
     const DevCsr& src = q.w_wire;
     const size_t m = q.m, n = q.n, nnz = src.nnz;

@@ -87,6 +87,14 @@ def first_unsatisfied(qap, weights):
     return qap.ctx.qap_check(qap.handle, weights)[1]
 
 
+def check_setup(qap, sigma, challenge=None):
+    """Is `sigma` a CRS of SOME trapdoor for `qap` (zk_crs_check)?  What a prover who did not run setup() asks once about the CRS it
+    was handed.  -> CrsCheck: .ok, .failed, .names, .flags.  Leave `challenge` None (drawn from the OS) outside tests."""
+    sigmag1, sigmag2 = sigma
+    assert sigmag1.crs is sigmag2.crs, "SigmaG1 / SigmaG2 come from different setups"
+    return qap.ctx.crs_check(sigmag1.crs, qap.handle, challenge)
+
+
 def verifying_key(sigma):
     """The VerifyingKey of a CRS: alpha, beta, gamma, delta and sum_gamma, all verify reads.  It serialises (to_bytes / save) and
     verifies single proofs on the host with no GPU; verify* below take it where they take `sigma`.  The batch calls run on the
