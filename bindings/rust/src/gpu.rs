@@ -54,6 +54,20 @@ pub struct ZkQapCheckResult { pub bad_gates: u32, pub first_bad: u32, pub flags:
 pub struct ZkCrsCheckResult { pub failed: u32, pub flags: u32 }   // zk_crs_check_result: ZK_CRS_CHECK_* bits
 pub const ZK_CRS_CHECK_T_ZERO: u32 = 1;                // flags: x is a root of t (consistent, unsound)
 pub const ZK_CRS_CHECK_LAGRANGE_PRESENT: u32 = 2;      // flags: the CRS carries Lagrange-basis arrays
+/// zk_crs_contribution: delta_before_g1 | delta_after_g1 | commit_g1 (8 words each) | response (4 words); its 224-byte memory image
+/// is its byte form (ZkCrsContribution::to_bytes / from_bytes)
+#[repr(C, align(8))]
+#[derive(Clone, Copy)]
+pub struct ZkCrsContribution(pub [u8; 224]);
+#[repr(C)]
+pub struct ZkCrsContributionResult { pub failed: u32, pub flags: u32 }   // zk_crs_contribution_result: ZK_CONTRIB_* bits
+pub const ZK_CONTRIB_UNCHANGED: u32 = 0x01;
+pub const ZK_CONTRIB_RECORD: u32 = 0x02;
+pub const ZK_CONTRIB_KNOWLEDGE: u32 = 0x04;
+pub const ZK_CONTRIB_DELTA_TWINS: u32 = 0x08;
+pub const ZK_CONTRIB_SUM_DELTA: u32 = 0x10;
+pub const ZK_CONTRIB_XI_T: u32 = 0x20;
+pub const ZK_CONTRIB_DEGENERATE: u32 = 0x40;
 #[repr(C)] pub struct ZkVk { _p: [u8; 0] }
 #[repr(C)]
 pub struct ZkVkDesc {                                    // zk_vk_desc
@@ -129,6 +143,13 @@ extern "C" {
                         out: *mut ZkQapCheckResult) -> c_int;
     // is the CRS a Groth16 CRS of some trapdoor for this QAP?  challenge = null: drawn from the OS inside the library
     fn zk_crs_check(ctx: *mut ZkCtx, crs: *const ZkCrs, qap: *const ZkQap, challenge: *const u64, out: *mut ZkCrsCheckResult) -> c_int;
+    // delta contributions: a new CRS with delta' = d delta (d = null: drawn from the OS, wiped), the record that proves knowledge of
+    // d for a 32-byte tag, and the check that `after` is `before` with only delta re-keyed
+    fn zk_crs_contribute(ctx: *mut ZkCtx, crs: *const ZkCrs, d: *const u64, tag: *const u8, out: *mut *mut ZkCrs,
+                         contribution: *mut ZkCrsContribution) -> c_int;
+    fn zk_crs_contribution_verify(c: *const ZkCrsContribution, tag: *const u8, ok: *mut c_int) -> c_int;
+    fn zk_crs_contribution_check(ctx: *mut ZkCtx, before: *const ZkCrs, after: *const ZkCrs, c: *const ZkCrsContribution, tag: *const u8,
+                                 challenge: *const u64, out: *mut ZkCrsContributionResult) -> c_int;
     // a stream of proofs: witnesses in page-locked host memory, two tickets in flight
     fn zk_host_alloc(bytes: usize, out: *mut *mut c_void) -> c_int;
     fn zk_host_free(p: *mut c_void);
@@ -637,6 +658,37 @@ impl GpuProver {
         let (failed, flags) = self.check_crs();
         failed == 0 && flags & ZK_CRS_CHECK_T_ZERO == 0
     }
+    /// Re-keys delta (zk_crs_contribute): the prover's CRS becomes the one setup would have made for (alpha, beta, gamma, delta d, x)
+    /// with a factor d drawn from the OS inside the library, wiped and never returned -- after which whoever made the old CRS no
+    /// longer knows this one's trapdoor.  Returns the record (a proof of knowledge of d bound to `tag`, the hash of the transcript so
+    /// far) and the new CRS in the reference's types, to be published.  The old CRS is checked against the new one before it is
+    /// dropped (check_contribution's relations); a failure there is a bug and panics.
+    pub fn contribute(&mut self, tag: &[u8; 32]) -> (ZkCrsContribution, (SigmaG1<G1Local>, SigmaG2<G2Local>)) {
+        let mut rec = ZkCrsContribution([0u8; 224]);
+        let mut next: *mut ZkCrs = std::ptr::null_mut();
+        let mut res = ZkCrsContributionResult { failed: 0, flags: 0 };
+        unsafe {
+            check(self.ctx.0, zk_crs_contribute(self.ctx.0, self.crs, std::ptr::null(), tag.as_ptr(), &mut next, &mut rec));
+            check(self.ctx.0, zk_crs_contribution_check(self.ctx.0, self.crs, next, &rec, tag.as_ptr(), std::ptr::null(), &mut res));
+            assert!(res.failed == 0, "zk_crs_contribute made a CRS its own check refuses: {:#x}", res.failed);
+            zk_crs_free(self.crs);
+        }
+        self.crs = next;
+        (rec, download_crs(&self.ctx, self.crs, self.n, self.m, self.input))
+    }
+    /// Is the CRS this prover holds `before` with only delta re-keyed, by whoever made `record` for `tag`?  (zk_crs_contribution_check:
+    /// the relations and their ZK_CONTRIB_* bits are in include/zkgpu.h.)  -> the failed bits, 0 = a valid successor; the prover's
+    /// CRS is then as good as `before` is (check_crs, once, for the first CRS of a chain).
+    pub fn check_contribution(&self, before: (&SigmaG1<G1Local>, &SigmaG2<G2Local>), record: &ZkCrsContribution, tag: &[u8; 32]) -> u32 {
+        let (old, n, m, l) = upload_crs(&self.ctx, before.0, before.1);
+        assert!(n == self.n && m == self.m && l == self.input, "CRS dimensions differ");
+        let mut res = ZkCrsContributionResult { failed: 0, flags: 0 };
+        unsafe {
+            check(self.ctx.0, zk_crs_contribution_check(self.ctx.0, old, self.crs, record, tag.as_ptr(), std::ptr::null(), &mut res));
+            zk_crs_free(old);
+        }
+        res.failed
+    }
     /// the same for `count` witnesses resident on the device, m elements each, `stride` elements apart (zk_witgen_run's layout: stride == m)
     pub fn check_witnesses_dev(&self, d_weights: *const c_void, m: usize, stride: usize, count: usize) -> Vec<ZkQapCheckResult> {
         let mut out: Vec<ZkQapCheckResult> = (0..count).map(|_| ZkQapCheckResult { bad_gates: 0, first_bad: ZK_QAP_CHECK_NONE, flags: 0 }).collect();
@@ -818,6 +870,17 @@ impl VerifyingKey {
     }
 }
 impl Drop for VerifyingKey { fn drop(&mut self) { unsafe { zk_vk_free(self.0) } } }   // safe before or after the prover's context goes
+
+impl ZkCrsContribution {
+    pub fn to_bytes(&self) -> [u8; 224] { self.0 }
+    pub fn from_bytes(b: &[u8; 224]) -> Self { ZkCrsContribution(*b) }
+    /// zk_crs_contribution_verify (host code, no GPU): does the record prove knowledge of d with delta_after = d delta_before for `tag`?
+    pub fn verify(&self, tag: &[u8; 32]) -> bool {
+        let mut ok = 0 as c_int;
+        assert_eq!(unsafe { zk_crs_contribution_verify(self, tag.as_ptr(), &mut ok) }, 0, "zk_crs_contribution_verify failed");
+        ok == 1
+    }
+}
 
 impl Drop for GpuProver {
     fn drop(&mut self) { unsafe { zk_crs_free(self.crs); zk_qap_free(self.qap); } }   // self.ctx drops afterwards (field order)

@@ -138,6 +138,13 @@ int zk_fq_batch(zk_ctx* ctx, int op, const uint64_t* a, const uint64_t* b, uint6
 /* out[i] = scalars[i] * points[i]  (exp_encrypted_g1 / exp_encrypted_g2, fr.rs:114-119) */
 int zk_g1_mul_batch(zk_ctx* ctx, const uint64_t* points, const uint64_t* scalars, uint64_t* out, size_t n);
 int zk_g2_mul_batch(zk_ctx* ctx, const uint64_t* points, const uint64_t* scalars, uint64_t* out, size_t n);
+/* out[i] = scalar * points[i], one canonical scalar < r for the whole array (0 allowed: every output is infinity).
+ * Same contract as zk_g1_mul_batch otherwise (canonical in / out, coordinate >= q or scalar >= r: ZK_ERR_RANGE); infinity entries
+ * (all-zero words) stay infinity, n = 0 does nothing, out may be points.  This is the routine zk_crs_contribute rescales the resident
+ * arrays with (csrc/crs_contribute.hip): the host splits the scalar by the curve's endomorphism and recodes both halves
+ * once, every lane walks the same digits, and a lane's four points share one field inversion.  Points are expected on the curve (as
+ * every CRS array is); for other input the output is unspecified. */
+int zk_g1_scale_batch(zk_ctx* ctx, const uint64_t* points, const uint64_t scalar[4], uint64_t* out, size_t n);
 /* out[i] = a[i] + b[i]  (Add for G1Local/G2Local, fr.rs:175-215) */
 int zk_g1_add_batch(zk_ctx* ctx, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n);
 int zk_g2_add_batch(zk_ctx* ctx, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n);
@@ -398,6 +405,76 @@ typedef struct {
 } zk_crs_check_result;
 int zk_crs_check(zk_ctx* ctx, const zk_crs* crs, const zk_qap* qap, const uint64_t challenge[4] /* NULL = drawn from the OS */,
                  zk_crs_check_result* out);
+
+/* A delta contribution: the other half of the workflow zk_crs_check belongs to (bellman's phase 2, `snarkjs zkey contribute`).  A
+ * party that receives a CRS multiplies delta by a secret factor d of its own: delta' = d delta.  Whoever ran zk_setup then no longer
+ * knows delta', and nobody has to trust them or run a whole setup again: one honest contributor in a chain is enough.
+ * zk_crs_contribute makes, on the same context, the CRS zk_setup would have made for the trapdoor (alpha, beta, gamma, delta d, x)
+ * -- byte for byte, for all four QAP forms:
+ *   delta_g1' = d delta_g1, delta_g2' = d delta_g2 (two points, host code);
+ *   sum_delta_g1' = d^-1 sum_delta_g1, xi_t_g1' = d^-1 xi_t_g1 and, when the source carries the Lagrange-basis arrays,
+ *   lagS_t1' = d^-1 lagS_t1: every point of a resident array times ONE scalar (k_g1_scale, csrc/crs_contribute.hip: the scalar is
+ *   split and recoded once on the host, every lane walks the same digits, four points share an inversion);
+ *   every other array (lag1 and lag2 included) is copied device to device.  The new CRS has no window tables: its first proof builds
+ *   them, as after zk_crs_upload.  zk_crs_save writes it as ZKCRSv1 / ZKCRSv2 like any CRS.
+ *  - d: canonical, 1 <= d < r; NULL draws it from the OS -- it is then never returned, and d, d^-1, the nonce and the recoded digits
+ *    are wiped before the call returns.  d = 0: ZK_ERR_DIV_BY_ZERO; d >= r: ZK_ERR_RANGE.  d = 1 gives an equal CRS.
+ *  - The source is read only (its tables and arrays are neither touched nor rebuilt): proofs over it before and after the call are
+ *    byte-equal, and an outstanding zk_prove_submit ticket is not disturbed.  Synchronous, on a stream of its own, complete on return.
+ *  - ZK_ERR_ARG: a null pointer (tag and d excepted) or a CRS of another context.  On every failure *out is NULL and *contribution is
+ *    untouched.
+ * The record is a Schnorr proof of knowledge of d, so that a contributor cannot merely cancel the contributions before theirs, bound
+ * to a 32-byte tag of the caller's (the hash of the transcript so far, or of whatever the ceremony publishes; NULL = 32 zero bytes):
+ *   T = k delta_before (k: a nonce from the OS),  c = SHA-256("ZKCONTRv1\0" | tag | delta_before | delta_after | T) read as a
+ *   big-endian integer and reduced mod r,  z = k + c d mod r;  it verifies iff z delta_before = T + c delta_after.
+ * A point enters the hash as its 64 bytes: the eight canonical little-endian words, x then y.  The struct's memory image (224 bytes,
+ * little-endian words) is its byte form.  zk_crs_contribution_prove / _verify are host code and take no context (as zk_vk_verify /
+ * zk_pairing).  prove: `nonce` NULL = drawn from the OS; a fixed nonce is for tests ONLY (two records with one nonce reveal d).
+ * ZK_ERR_RANGE for d or nonce >= r or a delta_before that is out of range, off the curve or infinity, ZK_ERR_DIV_BY_ZERO for d = 0.
+ * verify: a malformed field (coordinate >= q, off-curve point, response >= r, infinity delta_before or delta_after) gives *ok = 0
+ * with ZK_OK, like any record that does not verify. */
+typedef struct {
+    uint64_t delta_before_g1[8], delta_after_g1[8];   /* canonical affine */
+    uint64_t commit_g1[8];                            /* T = k * delta_before_g1 */
+    uint64_t response[4];                             /* z = k + c d mod r */
+} zk_crs_contribution;
+int zk_crs_contribution_prove(const uint64_t delta_before_g1[8], const uint64_t d[4], const uint64_t nonce[4] /* NULL = OS; fixed: tests only */,
+                              const uint8_t tag[32] /* NULL = 32 zero bytes */, zk_crs_contribution* out);
+int zk_crs_contribution_verify(const zk_crs_contribution* c, const uint8_t tag[32], int* ok);
+int zk_crs_contribute(zk_ctx* ctx, const zk_crs* crs, const uint64_t d[4] /* NULL = drawn from the OS, wiped, never returned */,
+                      const uint8_t tag[32], zk_crs** out, zk_crs_contribution* contribution);
+
+/* Is `after` the CRS `before` with only delta re-keyed, by someone who knew the factor?  A bit of out->failed per relation that
+ * does not hold (G = xi_g1[0], H = xi_g2[0] of `after`; rho_i = s^i over an array's own indices, s the challenge as in zk_crs_check):
+ *   UNCHANGED    alpha_g1, beta_g1, beta_g2, gamma_g2, xi_g1, xi_g2, sum_gamma_g1 are word for word the same (one compare kernel).
+ *   RECORD       the record's delta_before_g1 / delta_after_g1 are the two CRSs' delta_g1.
+ *   KNOWLEDGE    zk_crs_contribution_verify accepts the record for this tag.
+ *   DELTA_TWINS  e(delta_g1', H) = e(G, delta_g2').
+ *   SUM_DELTA    e(sum_i rho_i sum_delta_g1'[i], delta_g2') = e(sum_i rho_i sum_delta_g1[i], delta_g2).
+ *   XI_T         (n >= 2) the same over xi_t_g1.
+ *   DEGENERATE   delta_g1' or delta_g2' is infinity.
+ * Six pairings on the host; the random sums go through the MSM launcher over one-off tables on a stream of the call's own; both
+ * CRSs are read only.  The Lagrange-basis arrays are NOT looked at: zk_crs_check(after, qap) ties them to xi_g1, xi_g2 and xi_t_g1
+ * through its LAGRANGE relation.  "after is a valid successor of before" means failed == 0; "after is a good CRS" is then
+ * zk_crs_check(before, qap) once, for the head of the chain (the relations of zk_crs_check are invariant under delta -> d delta with
+ * sum_delta and xi_t divided by d, which is exactly what failed == 0 establishes).
+ * Soundness: as for zk_crs_check -- SUM_DELTA and XI_T are polynomial identities in s of degree below max(n, m), error <= max(n, m) / r
+ * for an s the maker of `after` could not predict; a fixed `challenge` is for tests, NULL draws 256 bits from the OS.
+ * ZK_ERR_ARG: a null pointer (tag and challenge excepted), CRSs that differ in (n, m, input), a handle of another context,
+ * challenge = 0.  ZK_ERR_RANGE: challenge >= r.  On every error *out is untouched. */
+#define ZK_CONTRIB_UNCHANGED 0x01u
+#define ZK_CONTRIB_RECORD 0x02u
+#define ZK_CONTRIB_KNOWLEDGE 0x04u
+#define ZK_CONTRIB_DELTA_TWINS 0x08u
+#define ZK_CONTRIB_SUM_DELTA 0x10u
+#define ZK_CONTRIB_XI_T 0x20u
+#define ZK_CONTRIB_DEGENERATE 0x40u
+typedef struct {
+    uint32_t failed;   /* ZK_CONTRIB_UNCHANGED .. ZK_CONTRIB_DEGENERATE: the relations that do not hold */
+    uint32_t flags;    /* reserved, 0 */
+} zk_crs_contribution_result;
+int zk_crs_contribution_check(zk_ctx* ctx, const zk_crs* before, const zk_crs* after, const zk_crs_contribution* c, const uint8_t tag[32],
+                              const uint64_t challenge[4] /* NULL = OS */, zk_crs_contribution_result* out);
 
 /* On-disk CRS container. The reference has no serialisation of SigmaG1/SigmaG2
  * (groth16/mod.rs:105-121), and setup (mod.rs:134-197) draws a fresh trapdoor on every call, so a CRS must be

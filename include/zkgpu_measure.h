@@ -52,9 +52,17 @@ int zk_profile_entry(const zk_ctx* ctx, int i, const char** name, double* total_
  * above (components with |limbs| < 2^29 and |value| < 8 q).  out holds 2 n residues, c0 then c1 of each element (8 words per
  * element); raw_out 18 limbs per element, c0's 9 then c1's 9.
  *   ZK_LAZY_FP2_MUL    (a + b i)(c + d i) 2^-261 = (a c - b d) 2^-261 + (a d + b c) 2^-261 i   (Fp2R::operator*)
- *   ZK_LAZY_FP2_SQR    (a + b i)^2 2^-261                                                   (Fp2R::sqr; operands a, b) */
+ *   ZK_LAZY_FP2_SQR    (a + b i)^2 2^-261                                                   (Fp2R::sqr; operands a, b)
+ * The scalar preparation of zk_g1_scale_batch / zk_crs_contribute (csrc/crs_contribution.hip: the GLV split and the width-4
+ * non-adjacent forms, host code) is reached through the same entry point, so that the test hook adds no symbol: HOST code, ctx may be
+ * NULL, field / b / c / d ignored.
+ *   ZK_LAZY_GLV_RECODE a: n scalars below r as eight 32-bit words each (little-endian); out: 4 words per scalar, |k1| (2 words) then
+ *                      |k2| (2 words), k = k1 + k2 lambda mod r; raw_out: ZK_GLV_RECODE_WORDS per scalar: k1 < 0, k2 < 0, the top
+ *                      digit position (-1 for k = 0), then ZK_GLV_RECODE_DIGITS signed digits of k1 and as many of k2 (position i
+ *                      weighs 2^i; the half's sign is folded into its digits) */
 enum { ZK_LAZY_MONT = 0, ZK_LAZY_SQR = 1, ZK_LAZY_MONT_DIFF = 2, ZK_LAZY_NORM = 3, ZK_LAZY_STORE = 4, ZK_LAZY_FR_REDUCE = 5, ZK_LAZY_FR_STORE = 6,
-       ZK_LAZY_FP2_MUL = 7, ZK_LAZY_FP2_SQR = 8 };
+       ZK_LAZY_FP2_MUL = 7, ZK_LAZY_FP2_SQR = 8, ZK_LAZY_GLV_RECODE = 9 };
+enum { ZK_GLV_RECODE_DIGITS = 132, ZK_GLV_RECODE_WORDS = 3 + 2 * 132 };
 int zk_lazy29_batch(zk_ctx* ctx, int field, int op, const int32_t* a, const int32_t* b, const int32_t* c, const int32_t* d, size_t n,
                     uint64_t* out, int32_t* raw_out);
 

@@ -24,6 +24,7 @@
 #pragma once
 #include <array>
 #include <cstdint>
+#include <cstring>
 #include <optional>
 #include <random>
 #include <stdexcept>
@@ -234,6 +235,8 @@ class QAP {
 namespace groth16 {
 
 // (SigmaG1, SigmaG2) (groth16/mod.rs:105-121), device resident
+using Tag = std::array<uint8_t, 32>;   // what a contribution record is bound to (contribute, below)
+struct Contribution;
 class Sigma {
    public:
     Sigma(Sigma&& o) noexcept : s_(std::exchange(o.s_, nullptr)) {}
@@ -249,6 +252,8 @@ class Sigma {
 
    private:
     friend Sigma setup_with(const Context&, const QAP&, const std::array<FrLocal, 5>&);
+    friend std::pair<Sigma, Contribution> contribute_with(const Context&, const Sigma&, const FrLocal&, const Tag&);
+    friend std::pair<Sigma, Contribution> contribute(const Context&, const Sigma&, const Tag&);
     explicit Sigma(zk_crs* s) : s_(s) {}
     zk_crs* s_;
 };
@@ -348,6 +353,60 @@ inline SetupCheck check_setup(const Context& c, const QAP& qap, const Sigma& sig
     zk_crs_check_result r{};
     c.check(zk_crs_check(c.get(), sigma.get(), qap.get(), nullptr, &r), "groth16::check_setup");
     return SetupCheck{r.failed, r.flags};
+}
+
+// Re-keying delta (zk_crs_contribute): what a party does to a CRS it was handed so that whoever ran setup no longer knows its
+// trapdoor.  contribute draws the factor d from the OS inside the library (it is wiped and never returned); contribute_with fixes
+// it and is for tests.  The Contribution proves knowledge of d for a 32-byte tag of the caller's (the hash of the transcript so
+// far); its 224 bytes are its byte form.  check_contribution: is `after` the CRS `before` with only delta re-keyed by whoever made
+// the record (zk_crs_contribution_check)?  `after` is then as good a CRS as `before` is (check_setup, once, for a chain's head).
+struct Contribution {
+    zk_crs_contribution raw{};
+    // zk_crs_contribution_verify: host code, no context
+    bool verify(const Tag& tag) const {
+        int ok = 0;
+        const int st = zk_crs_contribution_verify(&raw, tag.data(), &ok);
+        if (st != ZK_OK) throw Error(st, "Contribution::verify");
+        return ok != 0;
+    }
+    std::array<uint8_t, sizeof(zk_crs_contribution)> to_bytes() const {
+        std::array<uint8_t, sizeof(zk_crs_contribution)> b;
+        std::memcpy(b.data(), &raw, b.size());
+        return b;
+    }
+    static Contribution from_bytes(const std::array<uint8_t, sizeof(zk_crs_contribution)>& b) {
+        Contribution c;
+        std::memcpy(&c.raw, b.data(), b.size());
+        return c;
+    }
+};
+struct ContributionCheck {
+    uint32_t failed = 0;   // ZK_CONTRIB_UNCHANGED .. ZK_CONTRIB_DEGENERATE: the relations that do not hold
+    bool ok() const { return failed == 0; }
+    bool has(uint32_t bit) const { return (failed & bit) != 0; }
+};
+inline std::pair<Sigma, Contribution> contribute_with(const Context& c, const Sigma& sigma, const FrLocal& d, const Tag& tag) {
+    zk_crs* s = nullptr;
+    Contribution rec;
+    c.check(zk_crs_contribute(c.get(), sigma.get(), d.w.data(), tag.data(), &s, &rec.raw), "groth16::contribute");
+    return {Sigma(s), rec};
+}
+inline std::pair<Sigma, Contribution> contribute(const Context& c, const Sigma& sigma, const Tag& tag) {
+    zk_crs* s = nullptr;
+    Contribution rec;
+    c.check(zk_crs_contribute(c.get(), sigma.get(), nullptr, tag.data(), &s, &rec.raw), "groth16::contribute");
+    return {Sigma(s), rec};
+}
+inline ContributionCheck check_contribution_with(const Context& c, const Sigma& before, const Sigma& after, const Contribution& rec, const Tag& tag,
+                                                 const FrLocal& challenge) {
+    zk_crs_contribution_result r{};
+    c.check(zk_crs_contribution_check(c.get(), before.get(), after.get(), &rec.raw, tag.data(), challenge.w.data(), &r), "groth16::check_contribution");
+    return ContributionCheck{r.failed};
+}
+inline ContributionCheck check_contribution(const Context& c, const Sigma& before, const Sigma& after, const Contribution& rec, const Tag& tag) {
+    zk_crs_contribution_result r{};
+    c.check(zk_crs_contribution_check(c.get(), before.get(), after.get(), &rec.raw, tag.data(), nullptr, &r), "groth16::check_contribution");
+    return ContributionCheck{r.failed};
 }
 
 // groth16::verify((sigma_g1, sigma_g2), &inputs, proof) (mod.rs:299-320)

@@ -207,6 +207,98 @@ for _k, _n in enumerate(_lib.CRS_CHECK_BITS):
     setattr(CrsCheck, _n, 1 << _k)
 
 
+def _tag_arg(tag):
+    """a 32-byte tag as the u8 pointer the ABI takes (None = 32 zero bytes inside the library)"""
+    if tag is None:
+        return None, None
+    t = np.frombuffer(bytes(tag), dtype=np.uint8).copy()
+    if t.size != 32:
+        raise ValueError("the tag is 32 bytes")
+    return t, t.ctypes.data_as(_lib.u8p)
+
+
+def _fr_arg(x):
+    """None, an int or (4,) limbs -> (array kept alive, u64 pointer or None)"""
+    if x is None:
+        return None, None
+    return _u64(fr_to_limbs(x) if isinstance(x, int) else np.asarray(x).reshape(4))
+
+
+class Contribution:
+    """The record of a delta contribution (zk_crs_contribution): delta_g1 before and after, and a Schnorr proof of knowledge of the
+    factor bound to a 32-byte tag.  to_bytes / from_bytes: its 224-byte memory image (little-endian words)."""
+
+    def __init__(self, raw=None):
+        self.raw = raw if raw is not None else _lib.CrsContribution()
+
+    def to_bytes(self):
+        return bytes(bytearray(self.raw))
+
+    @classmethod
+    def from_bytes(cls, data):
+        data = bytes(data)
+        if len(data) != _lib.CONTRIBUTION_BYTES:
+            raise ValueError("a contribution record is %d bytes" % _lib.CONTRIBUTION_BYTES)
+        return cls(_lib.CrsContribution.from_buffer_copy(data))
+
+    def _words(self, name):
+        return np.array(list(getattr(self.raw, name)), dtype=np.uint64)
+
+    delta_before_g1 = property(lambda self: self._words("delta_before_g1"))
+    delta_after_g1 = property(lambda self: self._words("delta_after_g1"))
+    commit_g1 = property(lambda self: self._words("commit_g1"))
+    response = property(lambda self: limbs_to_int(self._words("response")))
+
+    def verify(self, tag=None):
+        """zk_crs_contribution_verify (host code): does the record prove knowledge of d with delta_after = d delta_before for `tag`?"""
+        t, tp = _tag_arg(tag)
+        ok = C.c_int(0)
+        rc = _lib.load().zk_crs_contribution_verify(C.byref(self.raw), tp, C.byref(ok))
+        if rc != 0:
+            raise ZkError(rc)
+        return bool(ok.value)
+
+    def __eq__(self, other):
+        return isinstance(other, Contribution) and self.to_bytes() == other.to_bytes()
+
+
+def contribution_prove(delta_before_g1, d, nonce=None, tag=None):
+    """zk_crs_contribution_prove (host code, no Context): the record for delta_after = d delta_before.  nonce: None = drawn from the
+    OS; a fixed one is for tests only."""
+    b, bp = _u64(np.asarray(delta_before_g1).reshape(8))
+    d_, dp = _fr_arg(d)
+    k_, kp = _fr_arg(nonce)
+    t, tp = _tag_arg(tag)
+    out = Contribution()
+    rc = _lib.load().zk_crs_contribution_prove(bp, dp, kp, tp, C.byref(out.raw))
+    if rc != 0:
+        raise ZkError(rc)
+    return out
+
+
+class ContributionCheck:
+    """What zk_crs_contribution_check found: `failed` = the ZK_CONTRIB_* bits of the relations that do not hold (class attributes
+    ContributionCheck.SUM_DELTA, ...); `names` lists them; `ok`: `after` is a valid successor of `before`."""
+
+    def __init__(self, failed, flags=0):
+        self.failed, self.flags = int(failed), int(flags)
+
+    @property
+    def ok(self):
+        return self.failed == 0
+
+    @property
+    def names(self):
+        return [n for k, n in enumerate(_lib.CONTRIB_BITS) if self.failed >> k & 1]
+
+    def __repr__(self):
+        return "ContributionCheck(failed=%s)" % ("|".join(self.names) or "0")
+
+
+for _k, _n in enumerate(_lib.CONTRIB_BITS):
+    setattr(ContributionCheck, _n, 1 << _k)
+
+
 class Context:
     def __init__(self, device=0):
         self.lib = _lib.load()
@@ -303,6 +395,14 @@ class Context:
 
     def g2_mul_batch(self, points, scalars):
         return self._pt2(self.lib.zk_g2_mul_batch, 16, points, scalars, 4)
+
+    def g1_scale_batch(self, points, scalar):
+        """zk_g1_scale_batch: every point times ONE scalar (an int or (4,) limbs) -> (n, 8) array."""
+        a, ap = _u64(np.asarray(points).reshape(-1, 8))
+        k_, kp = _fr_arg(scalar)
+        out = np.zeros_like(a)
+        self._check(self.lib.zk_g1_scale_batch(self.ptr, ap, kp, out.ctypes.data_as(_lib.u64p), a.shape[0]))
+        return out
 
     def g1_add_batch(self, a, b):
         return self._pt2(self.lib.zk_g1_add_batch, 8, a, b, 8)
@@ -418,6 +518,29 @@ class Context:
         out = _lib.CrsCheckResult(0xFFFFFFFF, 0xFFFFFFFF)
         self._check(self.lib.zk_crs_check(self.ptr, crs.ptr, qap.ptr, sp, C.byref(out)))
         return CrsCheck(out.failed, out.flags)
+
+    def crs_contribute(self, crs, d=None, tag=None):
+        """zk_crs_contribute: a new CRS whose delta is d times `crs`'s -- byte-equal to setup's for (alpha, beta, gamma, delta d, x) --
+        and the record that proves knowledge of d for `tag` (32 bytes, None = zeros).  d: None draws it from the OS inside the library
+        (it is wiped and never returned); an int in [1, r) or (4,) limbs fixes it.  -> (Crs, Contribution)"""
+        d_, dp = _fr_arg(d)
+        t, tp = _tag_arg(tag)
+        p = C.c_void_p()
+        rec = Contribution()
+        self._check(self.lib.zk_crs_contribute(self.ptr, crs.ptr, dp, tp, C.byref(p), C.byref(rec.raw)))
+        c = Crs(self, p, self.lib.zk_crs_free)
+        c.n, c.m, c.input = crs.n, crs.m, crs.input
+        return c, rec
+
+    def crs_contribution_check(self, before, after, contribution, tag=None, challenge=None):
+        """zk_crs_contribution_check: is `after` the CRS `before` with only delta re-keyed by whoever made `contribution` for `tag`?
+        -> ContributionCheck (.ok, .failed, .names).  challenge: None draws it from the OS (the only sound choice); an int in [1, r)
+        or (4,) limbs fixes it, for tests."""
+        s_, sp = _fr_arg(challenge)
+        t, tp = _tag_arg(tag)
+        out = _lib.CrsContributionResult(0xFFFFFFFF, 0xFFFFFFFF)
+        self._check(self.lib.zk_crs_contribution_check(self.ptr, before.ptr, after.ptr, C.byref(contribution.raw), tp, sp, C.byref(out)))
+        return ContributionCheck(out.failed, out.flags)
 
     def qap_weighted_sum(self, qap, weights, which):
         """sum_i weights[i] * u_i / v_i / w_i (which = 0 / 1 / 2; mod.rs:233-253): coefficients (dense QAP) or values on the domain

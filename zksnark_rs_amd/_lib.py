@@ -25,6 +25,9 @@ QAP_CHECK_CHUNK_LANES = 1 << 28  # ZK_QAP_CHECK_CHUNK_LANES
 CRS_CHECK_BITS = ("GENERATORS", "POWERS_G1", "POWERS_G2", "TWINS", "XI_T", "WIRES", "WIRES_GAMMA", "WIRES_DELTA", "LAGRANGE", "DEGENERATE")
 CRS_CHECK_T_ZERO = 1             # ZK_CRS_CHECK_T_ZERO
 CRS_CHECK_LAGRANGE_PRESENT = 2   # ZK_CRS_CHECK_LAGRANGE_PRESENT
+# zk_crs_contribution_result.failed (ZK_CONTRIB_*), in bit order
+CONTRIB_BITS = ("UNCHANGED", "RECORD", "KNOWLEDGE", "DELTA_TWINS", "SUM_DELTA", "XI_T", "DEGENERATE")
+CONTRIBUTION_BYTES = 224         # sizeof(zk_crs_contribution): its memory image is its byte form
 
 u64p = C.POINTER(C.c_uint64)
 u32p = C.POINTER(C.c_uint32)
@@ -63,6 +66,14 @@ class QapCheckResult(C.Structure):
 
 
 class CrsCheckResult(C.Structure):
+    _fields_ = [("failed", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class CrsContribution(C.Structure):
+    _fields_ = [("delta_before_g1", C.c_uint64 * 8), ("delta_after_g1", C.c_uint64 * 8), ("commit_g1", C.c_uint64 * 8), ("response", C.c_uint64 * 4)]
+
+
+class CrsContributionResult(C.Structure):
     _fields_ = [("failed", C.c_uint32), ("flags", C.c_uint32)]
 
 
@@ -107,6 +118,7 @@ SIGNATURES = {
     "zk_fq_batch": (C.c_int, [C.c_void_p, C.c_int, u64p, u64p, u64p, C.c_size_t]),
     "zk_g1_mul_batch": (C.c_int, [C.c_void_p, u64p, u64p, u64p, C.c_size_t]),
     "zk_g2_mul_batch": (C.c_int, [C.c_void_p, u64p, u64p, u64p, C.c_size_t]),
+    "zk_g1_scale_batch": (C.c_int, [C.c_void_p, u64p, u64p, u64p, C.c_size_t]),
     "zk_g1_add_batch": (C.c_int, [C.c_void_p, u64p, u64p, u64p, C.c_size_t]),
     "zk_g2_add_batch": (C.c_int, [C.c_void_p, u64p, u64p, u64p, C.c_size_t]),
     "zk_qap_upload_sparse": (C.c_int, [C.c_void_p, C.POINTER(QapSparseDesc), C.POINTER(C.c_void_p)]),
@@ -138,6 +150,11 @@ SIGNATURES = {
     "zk_crs_upload": (C.c_int, [C.c_void_p, C.POINTER(CrsDesc), C.POINTER(C.c_void_p)]),
     "zk_setup": (C.c_int, [C.c_void_p, C.c_void_p, u64p, C.POINTER(C.c_void_p)]),
     "zk_crs_check": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, u64p, C.POINTER(CrsCheckResult)]),
+    "zk_crs_contribution_prove": (C.c_int, [u64p, u64p, u64p, u8p, C.POINTER(CrsContribution)]),
+    "zk_crs_contribution_verify": (C.c_int, [C.POINTER(CrsContribution), u8p, C.POINTER(C.c_int)]),
+    "zk_crs_contribute": (C.c_int, [C.c_void_p, C.c_void_p, u64p, u8p, C.POINTER(C.c_void_p), C.POINTER(CrsContribution)]),
+    "zk_crs_contribution_check": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CrsContribution), u8p, u64p,
+                                            C.POINTER(CrsContributionResult)]),
     "zk_crs_dims": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "zk_crs_download": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(CrsOut)]),
     "zk_crs_free": (None, [C.c_void_p]),

@@ -7,6 +7,7 @@
 #include "kernels.hpp"
 #include "pipeline.hpp"
 #include "interp.hpp"
+#include "crs_contribution.hpp"
 
 using namespace zk;
 
@@ -226,6 +227,25 @@ int zk_msm_g2(zk_ctx* ctx, const uint64_t* points, const uint64_t* scalars, size
     return guarded(ctx, [&] { msm_host<Fq2>(ctx, points, scalars, n, window_bits, out); ctx->resolve_profile(); });
 }
 int zk_lazy29_batch(zk_ctx* ctx, int field, int op, const int32_t* a, const int32_t* b, const int32_t* c, const int32_t* d, size_t n, uint64_t* out, int32_t* raw_out) {
+    if (op == ZK_LAZY_GLV_RECODE) {   // host code, no context: the one scalar of k_g1_scale as the kernel receives it (zkgpu_measure.h)
+        if (!a || !out || !raw_out) return ZK_ERR_ARG;
+        return guarded(nullptr, [&] {
+            for (size_t e = 0; e < n; ++e) {
+                const uint32_t* k = reinterpret_cast<const uint32_t*>(a) + 8 * e;
+                uint32_t k1[5], k2[5];
+                bool n1, n2;
+                glv_split_host(k, k1, n1, k2, n2);
+                ZK_REQUIRE(k1[4] == 0 && k2[4] == 0, ZK_ERR_SIZE, "glv_split: a half of 2^128 or more");
+                out[4 * e] = k1[0] | ((uint64_t)k1[1] << 32); out[4 * e + 1] = k1[2] | ((uint64_t)k1[3] << 32);
+                out[4 * e + 2] = k2[0] | ((uint64_t)k2[1] << 32); out[4 * e + 3] = k2[2] | ((uint64_t)k2[3] << 32);
+                ScaleDigits dg;
+                scalar_recode(k, dg);
+                int32_t* r = raw_out + (size_t)ZK_GLV_RECODE_WORDS * e;
+                r[0] = n1; r[1] = n2; r[2] = dg.top;
+                for (int i = 0; i < ZK_GLV_RECODE_DIGITS; ++i) { r[3 + i] = dg.d1[i]; r[3 + ZK_GLV_RECODE_DIGITS + i] = dg.d2[i]; }
+            }
+        });
+    }
     if (!ctx) return ZK_ERR_ARG;
     return guarded(ctx, [&] { lazy29_batch(ctx, field, op, a, b, c, d, n, out, raw_out); });
 }

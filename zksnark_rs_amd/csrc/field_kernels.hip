@@ -177,13 +177,17 @@ void point_mul_batch(zk_ctx* ctx, const uint64_t* points, const uint64_t* scalar
     ZK_HIP(hipMemcpyAsync(dp.p, points, n * sizeof(Aff<F>), hipMemcpyHostToDevice, ctx->stream));
     ZK_HIP(hipMemcpyAsync(ds.p, scalars, n * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
     ZK_HIP(hipMemsetAsync(flag.p, 0, sizeof(int), ctx->stream));
-    hipLaunchKernelGGL(k_point_mul<F>, dim3(ceil_div(n, 64)), dim3(64), 0, ctx->stream, dp.p, ds.p, dout.p, n, flag.p);
+    {
+        ProfScope ps(ctx, "point_mul", (2.0 * sizeof(Aff<F>) + sizeof(Fr)) * n);
+        hipLaunchKernelGGL(k_point_mul<F>, dim3(ceil_div(n, 64)), dim3(64), 0, ctx->stream, dp.p, ds.p, dout.p, n, flag.p);
+    }
     ZK_HIP(hipGetLastError());
     int hflag = 0;
     ZK_HIP(hipMemcpyAsync(&hflag, flag.p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     ZK_HIP(hipMemcpyAsync(out, dout.p, n * sizeof(Aff<F>), hipMemcpyDeviceToHost, ctx->stream));
     ZK_HIP(hipStreamSynchronize(ctx->stream));
     ZK_REQUIRE(!hflag, ZK_ERR_RANGE, "coordinate or scalar >= modulus");
+    ctx->resolve_profile();
 }
 // canonical <-> Montgomery coordinates of whole arrays (the affine pair sums work on device-form points)
 template <class F>

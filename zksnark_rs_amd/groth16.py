@@ -95,6 +95,25 @@ def check_setup(qap, sigma, challenge=None):
     return qap.ctx.crs_check(sigmag1.crs, qap.handle, challenge)
 
 
+def contribute(sigma, d=None, tag=None):
+    """Re-key delta: a new (SigmaG1, SigmaG2) whose delta is d times `sigma`'s, and the Contribution that proves knowledge of d for
+    `tag` (zk_crs_contribute).  Leave d None (drawn from the OS inside the library, wiped, never returned) outside tests.  What a
+    party does to a CRS it was handed so that whoever ran setup() no longer knows its trapdoor."""
+    sigmag1, sigmag2 = sigma
+    assert sigmag1.crs is sigmag2.crs, "SigmaG1 / SigmaG2 come from different setups"
+    crs, record = sigmag1.ctx.crs_contribute(sigmag1.crs, d, tag)
+    shared = {}
+    return (SigmaG1(sigmag1.ctx, crs, shared), SigmaG2(sigmag1.ctx, crs, shared)), record
+
+
+def check_contribution(before, after, contribution, tag=None, challenge=None):
+    """Is `after` the CRS `before` with only delta re-keyed, by whoever made `contribution` for `tag` (zk_crs_contribution_check)?
+    -> ContributionCheck: .ok, .failed, .names.  `after` is then as good a CRS as `before` (check_setup, once, for the first CRS of
+    a chain).  Leave `challenge` None outside tests."""
+    assert before[0].crs is before[1].crs and after[0].crs is after[1].crs, "SigmaG1 / SigmaG2 come from different setups"
+    return before[0].ctx.crs_contribution_check(before[0].crs, after[0].crs, contribution, tag, challenge)
+
+
 def verifying_key(sigma):
     """The VerifyingKey of a CRS: alpha, beta, gamma, delta and sum_gamma, all verify reads.  It serialises (to_bytes / save) and
     verifies single proofs on the host with no GPU; verify* below take it where they take `sigma`.  The batch calls run on the
