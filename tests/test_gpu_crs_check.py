@@ -13,6 +13,7 @@ from zksnark_rs_amd import CrsCheck, SplitMix64, _lib, ints_to_limbs, limbs_to_i
 from zksnark_rs_amd.circuits import chain_rows, chain_weights
 
 import crs_check_model as ccm
+from crs_container import read_v2
 from setup_edge_cases import on_domain_trapdoor
 from test_crs_check_model import build_case, challenges, tamper_targets
 from test_integer_roots import chain_rows_integers, chain_weights_integers
@@ -57,17 +58,6 @@ def fnv1a(data):
     for b in data:
         h = ((h ^ b) * 0x100000001b3) & 0xFFFFFFFFFFFFFFFF
     return h
-
-
-def read_v2(path, n):
-    """(header fields, v1 payload bytes, dict of the three Lagrange-basis arrays) of a ZKCRSv2 file"""
-    raw = open(path, "rb").read()
-    assert raw[:8] == b"ZKCRSv2\0"
-    tail = 8 * (8 * n + 8 * (n - 1) + 16 * n)
-    body = np.frombuffer(raw[len(raw) - tail:], dtype=np.uint64)
-    lag = dict(lag1=body[:8 * n].reshape(n, 8).copy(), lagS_t1=body[8 * n:8 * n + 8 * (n - 1)].reshape(n - 1, 8).copy(),
-               lag2=body[8 * n + 8 * (n - 1):].reshape(n, 16).copy())
-    return raw[8:32], raw[40:len(raw) - tail], lag
 
 
 def write_v2(path, dims, payload, lag):
