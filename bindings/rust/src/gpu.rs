@@ -51,6 +51,16 @@ pub struct ZkQapSparseDesc { log_n: c_uint, m: usize, input: usize, u: ZkSparseR
 #[repr(C)]
 pub struct ZkQapCheckResult { pub bad_gates: u32, pub first_bad: u32, pub flags: u32 }   // zk_qap_check_result (12 bytes)
 #[repr(C)]
+pub struct ZkPowersDesc {                                // zk_powers_desc: a powers-of-tau transcript, canonical affine words
+    n_tau_g1: usize, n_rest: usize,
+    tau_g1: *const u64, tau_g2: *const u64, alpha_tau_g1: *const u64, beta_tau_g1: *const u64, beta_g2: *const u64,
+}
+/// A powers-of-tau transcript as GpuProver::from_powers takes it: 8 words per G1 point, 16 per G2 point, canonical affine,
+/// little-endian; tau_g1 holds at least 2n - 1 points, tau_g2 / alpha_tau_g1 / beta_tau_g1 one common count of at least n.
+pub struct PowersOfTau<'a> {
+    pub tau_g1: &'a [u64], pub tau_g2: &'a [u64], pub alpha_tau_g1: &'a [u64], pub beta_tau_g1: &'a [u64], pub beta_g2: &'a [u64; 16],
+}
+#[repr(C)]
 pub struct ZkCrsCheckResult { pub failed: u32, pub flags: u32 }   // zk_crs_check_result: ZK_CRS_CHECK_* bits
 pub const ZK_CRS_CHECK_T_ZERO: u32 = 1;                // flags: x is a root of t (consistent, unsound)
 pub const ZK_CRS_CHECK_LAGRANGE_PRESENT: u32 = 2;      // flags: the CRS carries Lagrange-basis arrays
@@ -143,6 +153,8 @@ extern "C" {
                         out: *mut ZkQapCheckResult) -> c_int;
     // is the CRS a Groth16 CRS of some trapdoor for this QAP?  challenge = null: drawn from the OS inside the library
     fn zk_crs_check(ctx: *mut ZkCtx, crs: *const ZkCrs, qap: *const ZkQap, challenge: *const u64, out: *mut ZkCrsCheckResult) -> c_int;
+    // the head of a ceremony: the QAP's CRS from a powers-of-tau transcript, gamma = delta = 1, group operations only
+    fn zk_crs_from_powers(ctx: *mut ZkCtx, qap: *const ZkQap, powers: *const ZkPowersDesc, out: *mut *mut ZkCrs) -> c_int;
     // delta contributions: a new CRS with delta' = d delta (d = null: drawn from the OS, wiped), the record that proves knowledge of
     // d for a 32-byte tag, and the check that `after` is `before` with only delta re-keyed
     fn zk_crs_contribute(ctx: *mut ZkCtx, crs: *const ZkCrs, d: *const u64, tag: *const u8, out: *mut *mut ZkCrs,
@@ -657,6 +669,29 @@ impl GpuProver {
     pub fn crs_is_good(&self) -> bool {
         let (failed, flags) = self.check_crs();
         failed == 0 && flags & ZK_CRS_CHECK_T_ZERO == 0
+    }
+    /// The head of a trustless setup (zk_crs_from_powers): the prover's CRS becomes the one setup would have made for (alpha, beta, 1,
+    /// 1, x) with the (alpha, beta, x) of a powers-of-tau transcript that nobody has to know -- derived by group operations only, for
+    /// a prover built by from_root_rep (roots of unity) or from_root_rep_integers; the other forms panic with the library's
+    /// "unsupported" text.  The transcript is NOT checked to be a sequence of powers: the derived CRS goes through check_crs before it
+    /// replaces the old one, and a transcript that fails it panics.  Then one `contribute` per party.  Returns the new CRS in the
+    /// reference's types, to be published.
+    pub fn from_powers(&mut self, powers: &PowersOfTau) -> (SigmaG1<G1Local>, SigmaG2<G2Local>) {
+        let n_rest = powers.tau_g2.len() / 16;
+        assert!(powers.tau_g1.len() % 8 == 0 && powers.tau_g2.len() % 16 == 0, "a G1 point is 8 words, a G2 point 16");
+        assert!(powers.alpha_tau_g1.len() == 8 * n_rest && powers.beta_tau_g1.len() == 8 * n_rest, "tau_g2, alpha_tau_g1, beta_tau_g1 differ in length");
+        let desc = ZkPowersDesc { n_tau_g1: powers.tau_g1.len() / 8, n_rest, tau_g1: powers.tau_g1.as_ptr(), tau_g2: powers.tau_g2.as_ptr(),
+                                  alpha_tau_g1: powers.alpha_tau_g1.as_ptr(), beta_tau_g1: powers.beta_tau_g1.as_ptr(), beta_g2: powers.beta_g2.as_ptr() };
+        let mut next: *mut ZkCrs = std::ptr::null_mut();
+        let mut res = ZkCrsCheckResult { failed: 0, flags: 0 };
+        unsafe {
+            check(self.ctx.0, zk_crs_from_powers(self.ctx.0, self.qap, &desc, &mut next));
+            check(self.ctx.0, zk_crs_check(self.ctx.0, next, self.qap, std::ptr::null(), &mut res));
+            assert!(res.failed == 0 && res.flags & ZK_CRS_CHECK_T_ZERO == 0, "the transcript is no powers-of-tau sequence: zk_crs_check {:#x}", res.failed);
+            zk_crs_free(self.crs);
+        }
+        self.crs = next;
+        download_crs(&self.ctx, self.crs, self.n, self.m, self.input)
     }
     /// Re-keys delta (zk_crs_contribute): the prover's CRS becomes the one setup would have made for (alpha, beta, gamma, delta d, x)
     /// with a factor d drawn from the OS inside the library, wiped and never returned -- after which whoever made the old CRS no

@@ -476,6 +476,44 @@ typedef struct {
 int zk_crs_contribution_check(zk_ctx* ctx, const zk_crs* before, const zk_crs* after, const zk_crs_contribution* c, const uint8_t tag[32],
                               const uint64_t challenge[4] /* NULL = OS */, zk_crs_contribution_result* out);
 
+/* The head of such a chain WITHOUT a trapdoor: derive the circuit's CRS from a universal powers-of-tau transcript by group operations
+ * only (what bellman's MPCParameters::new and `snarkjs zkey new` do), with gamma = delta = 1.  zk_setup takes (alpha, beta, gamma,
+ * delta, x) as an argument, so whoever runs it knows x, alpha and beta for good, and a delta contribution removes delta only.
+ * The result is the CRS zk_setup(qap, (alpha, beta, 1, 1, x)) would make -- byte for byte in every array zk_crs_download returns and,
+ * for the integer-roots form, in the Lagrange-basis arrays a ZKCRSv2 file carries -- for the (alpha, beta, x) of the transcript:
+ *   alpha_g1 = alpha_tau_g1[0], beta_g1 = beta_tau_g1[0], beta_g2 copied; delta_g1 = tau_g1[0]; gamma_g2 = delta_g2 = tau_g2[0];
+ *   xi_g1 = tau_g1[0..n), xi_g2 = tau_g2[0..n);
+ *   wire i: sum_j u_ij [beta L_j]_1 + v_ij [alpha L_j]_1 + w_ij [L_j]_1 (L_j: the Lagrange polynomial of gate j), wires 0..l to
+ *   sum_gamma_g1 and the rest to sum_delta_g1 (k_wire_points, csrc/crs_from_powers.hip: a sparse matrix times a vector of points);
+ *   xi_t_g1[k] = [x^k t(x)]_1, k <= n - 2.
+ * QAP forms:
+ *   roots of unity (zk_qap_upload_sparse)            the three arrays [L_j], [alpha L_j], [beta L_j] are inverse transforms over n points
+ *                                                    of tau_g1, alpha_tau_g1, beta_tau_g1; xi_t_g1[k] = tau_g1[n + k] - tau_g1[k].
+ *   integer roots (zk_qap_upload_sparse_integers)    the three arrays come from the transposed interpolation tree (csrc/gbasis.hip);
+ *                                                    xi_t_g1[k] = sum_{j<=n} t_j tau_g1[k + j], a cyclic convolution of 2^ceil(log2(2n-1))
+ *                                                    points; the Lagrange-basis arrays of the result are attached (n <= 2^22).
+ *   arbitrary roots, dense                           ZK_ERR_UNSUPPORTED (zk_last_error says which form was given).
+ * Points are canonical affine host arrays as in zk_crs_desc; the point at infinity (all words zero) is accepted anywhere.  Powers
+ * beyond the first 2n - 1 of tau_g1 and the first n of the other arrays are ignored.
+ * The call does NOT check that the arrays are a powers-of-tau sequence (tau_g1[k+1] = x tau_g1[k], the same x in G2, alpha and beta
+ * the same in every entry): run zk_crs_check(result, qap), which covers every array derived here (POWERS_G1, POWERS_G2, TWINS, XI_T,
+ * WIRES, LAGRANGE), before anyone contributes to or proves with the result.
+ *  - Synchronous, on a stream of its own; an outstanding zk_prove_submit ticket is not disturbed.  The new CRS has no window tables:
+ *    its first proof builds them, as after zk_crs_upload.
+ *  - ZK_ERR_ARG: a null pointer (arrays of the desc included), a QAP of another context, n_tau_g1 < 2n - 1, n_rest < n.
+ *    ZK_ERR_RANGE: a coordinate >= q, a point off its curve, a G2 point outside the subgroup of order r (zk_crs_upload's statuses).
+ *    On every failure *out is NULL and the context and the QAP stay usable. */
+typedef struct {
+    size_t n_tau_g1;               /* number of tau_g1 points, >= 2n-1 for a QAP of n gates */
+    size_t n_rest;                 /* number of points in each of the other three arrays, >= n */
+    const uint64_t* tau_g1;        /* [x^k]_1        k < n_tau_g1 */
+    const uint64_t* tau_g2;        /* [x^k]_2        k < n_rest   */
+    const uint64_t* alpha_tau_g1;  /* [alpha x^k]_1  k < n_rest   */
+    const uint64_t* beta_tau_g1;   /* [beta  x^k]_1  k < n_rest   */
+    const uint64_t* beta_g2;       /* [beta]_2 */
+} zk_powers_desc;
+int zk_crs_from_powers(zk_ctx* ctx, const zk_qap* qap, const zk_powers_desc* powers, zk_crs** out);
+
 /* On-disk CRS container. The reference has no serialisation of SigmaG1/SigmaG2
  * (groth16/mod.rs:105-121), and setup (mod.rs:134-197) draws a fresh trapdoor on every call, so a CRS must be
  * written down to be reused.  Format: "ZKCRSv1\0", n, m, input, FNV-1a-64 of the payload, then the arrays of

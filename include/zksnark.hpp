@@ -237,6 +237,12 @@ namespace groth16 {
 // (SigmaG1, SigmaG2) (groth16/mod.rs:105-121), device resident
 using Tag = std::array<uint8_t, 32>;   // what a contribution record is bound to (contribute, below)
 struct Contribution;
+// A powers-of-tau transcript (setup_from_powers, below): canonical affine words, 8 per G1 point and 16 per G2 point.  tau_g1 holds at
+// least 2n - 1 points for a QAP of n gates; tau_g2, alpha_tau_g1 and beta_tau_g1 one common count of at least n.
+struct PowersOfTau {
+    std::vector<uint64_t> tau_g1, tau_g2, alpha_tau_g1, beta_tau_g1;
+    std::array<uint64_t, ZK_G2_WORDS> beta_g2{};
+};
 class Sigma {
    public:
     Sigma(Sigma&& o) noexcept : s_(std::exchange(o.s_, nullptr)) {}
@@ -252,6 +258,7 @@ class Sigma {
 
    private:
     friend Sigma setup_with(const Context&, const QAP&, const std::array<FrLocal, 5>&);
+    friend Sigma setup_from_powers(const Context&, const QAP&, const PowersOfTau&);
     friend std::pair<Sigma, Contribution> contribute_with(const Context&, const Sigma&, const FrLocal&, const Tag&);
     friend std::pair<Sigma, Contribution> contribute(const Context&, const Sigma&, const Tag&);
     explicit Sigma(zk_crs* s) : s_(s) {}
@@ -303,6 +310,21 @@ inline Sigma setup(const Context& c, const QAP& qap) {
     std::array<FrLocal, 5> td;
     for (auto& t : td) do { t = FrLocal::random_elem(); } while (t == FrLocal(0));
     return setup_with(c, qap, td);
+}
+
+// What a ceremony starts from instead of setup (zk_crs_from_powers): the QAP's CRS derived from a powers-of-tau transcript by group
+// operations only, with gamma = delta = 1 -- the CRS setup_with(c, qap, {alpha, beta, 1, 1, x}) makes, for an (alpha, beta, x) nobody
+// has to know.  QAP::from_sparse (rows over the roots 1..n); QAP::from, from_dense and from_root_rep throw ZK_ERR_UNSUPPORTED.  The transcript is NOT checked to
+// be a sequence of powers: check_setup(c, qap, sigma) on the result, then one contribute per party, each checked by check_contribution.
+inline Sigma setup_from_powers(const Context& c, const QAP& qap, const PowersOfTau& p) {
+    if (p.tau_g1.size() % ZK_G1_WORDS || p.tau_g2.size() % ZK_G2_WORDS || p.alpha_tau_g1.size() * 2 != p.tau_g2.size() ||
+        p.beta_tau_g1.size() * 2 != p.tau_g2.size())
+        throw Error(ZK_ERR_ARG, "groth16::setup_from_powers: tau_g2, alpha_tau_g1 and beta_tau_g1 must hold the same number of whole points");
+    zk_powers_desc d{p.tau_g1.size() / ZK_G1_WORDS, p.tau_g2.size() / ZK_G2_WORDS, p.tau_g1.data(), p.tau_g2.data(), p.alpha_tau_g1.data(),
+                     p.beta_tau_g1.data(), p.beta_g2.data()};
+    zk_crs* s = nullptr;
+    c.check(zk_crs_from_powers(c.get(), qap.get(), &d, &s), "groth16::setup_from_powers");
+    return Sigma(s);
 }
 
 // prove with the blinding scalars given

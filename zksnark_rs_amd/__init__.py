@@ -542,6 +542,25 @@ class Context:
         self._check(self.lib.zk_crs_contribution_check(self.ptr, before.ptr, after.ptr, C.byref(contribution.raw), tp, sp, C.byref(out)))
         return ContributionCheck(out.failed, out.flags)
 
+    def crs_from_powers(self, qap, tau_g1, tau_g2, alpha_tau_g1, beta_tau_g1, beta_g2):
+        """zk_crs_from_powers: the CRS of `qap` (roots-of-unity or integer-roots form) from a powers-of-tau transcript, by group
+        operations only -- byte-equal to setup(qap, (alpha, beta, 1, 1, x)) for the transcript's (alpha, beta, x).  tau_g1: (>= 2n-1, 8)
+        points [x^k]_1; tau_g2 (>= n, 16), alpha_tau_g1, beta_tau_g1 (>= n, 8) of one common length; beta_g2: (16,).  The transcript is
+        NOT checked to be a sequence of powers: run crs_check(result, qap).  -> Crs"""
+        t1, t1p = _u64(np.asarray(tau_g1).reshape(-1, 8))
+        t2, t2p = _u64(np.asarray(tau_g2).reshape(-1, 16))
+        a1, a1p = _u64(np.asarray(alpha_tau_g1).reshape(-1, 8))
+        b1, b1p = _u64(np.asarray(beta_tau_g1).reshape(-1, 8))
+        b2, b2p = _u64(np.asarray(beta_g2).reshape(16))
+        if not (t2.shape[0] == a1.shape[0] == b1.shape[0]):
+            raise ValueError("tau_g2, alpha_tau_g1 and beta_tau_g1 differ in length")
+        d = _lib.PowersDesc(t1.shape[0], t2.shape[0], t1p, t2p, a1p, b1p, b2p)
+        p = C.c_void_p()
+        self._check(self.lib.zk_crs_from_powers(self.ptr, qap.ptr, C.byref(d), C.byref(p)))
+        c = Crs(self, p, self.lib.zk_crs_free)
+        c.n, c.m, c.input = qap.n, qap.m, qap.input
+        return c
+
     def qap_weighted_sum(self, qap, weights, which):
         """sum_i weights[i] * u_i / v_i / w_i (which = 0 / 1 / 2; mod.rs:233-253): coefficients (dense QAP) or values on the domain
         (sparse QAP, u and v only) as an (n, 4) uint64 array."""

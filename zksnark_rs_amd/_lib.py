@@ -57,6 +57,11 @@ class CrsOut(C.Structure):
                 ("beta_g2", u64p), ("gamma_g2", u64p), ("delta_g2", u64p), ("xi_g2", u64p)]
 
 
+class PowersDesc(C.Structure):
+    _fields_ = [("n_tau_g1", C.c_size_t), ("n_rest", C.c_size_t), ("tau_g1", u64p), ("tau_g2", u64p),
+                ("alpha_tau_g1", u64p), ("beta_tau_g1", u64p), ("beta_g2", u64p)]
+
+
 class VkDesc(C.Structure):
     _fields_ = [("input", C.c_size_t), ("alpha_g1", u64p), ("beta_g2", u64p), ("gamma_g2", u64p), ("delta_g2", u64p), ("sum_gamma_g1", u64p)]
 
@@ -155,6 +160,7 @@ SIGNATURES = {
     "zk_crs_contribute": (C.c_int, [C.c_void_p, C.c_void_p, u64p, u8p, C.POINTER(C.c_void_p), C.POINTER(CrsContribution)]),
     "zk_crs_contribution_check": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CrsContribution), u8p, u64p,
                                             C.POINTER(CrsContributionResult)]),
+    "zk_crs_from_powers": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(PowersDesc), C.POINTER(C.c_void_p)]),
     "zk_crs_dims": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "zk_crs_download": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(CrsOut)]),
     "zk_crs_free": (None, [C.c_void_p]),

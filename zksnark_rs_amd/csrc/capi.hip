@@ -311,6 +311,11 @@ int zk_setup(zk_ctx* ctx, const zk_qap* qap, const uint64_t trapdoor[20], zk_crs
     *out = nullptr;
     return guarded(ctx, [&] { *out = crs_setup(ctx, *qap, trapdoor); });
 }
+int zk_crs_from_powers(zk_ctx* ctx, const zk_qap* qap, const zk_powers_desc* powers, zk_crs** out) {
+    if (out) *out = nullptr;
+    if (!ctx || !qap || !powers || !out) return ZK_ERR_ARG;
+    return guarded(ctx, [&] { *out = crs_from_powers(ctx, *qap, *powers); ctx->resolve_profile(); });
+}
 int zk_crs_dims(const zk_crs* crs, size_t* n, size_t* m, size_t* input) {
     if (!crs) return ZK_ERR_ARG;
     crs_dims(*crs, n, m, input);

@@ -49,7 +49,7 @@ __global__ void k_g2_times_r(const P* __restrict__ pts, size_t n, int* flag) {
     for (int w = 0; w < 8; ++w) r[w] = FrParams::P[w];
     if (!jac_mul_words(p, r).is_inf()) atomicOr(flag, 8);
 }
-static void g2_subgroup_check(zk_ctx* ctx, const G2A* d_pts, size_t n, int* d_flag) {
+void g2_subgroup_check(zk_ctx* ctx, const G2A* d_pts, size_t n, int* d_flag) {
     if (!n) return;
     if (n <= 4096) {
         hipLaunchKernelGGL(k_g2_times_r<G2A>, dim3(ceil_div(n, 64)), dim3(64), 0, ctx->stream, d_pts, n, d_flag);

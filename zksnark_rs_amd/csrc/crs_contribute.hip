@@ -361,6 +361,10 @@ void contribution_check(zk_ctx* ctx, const zk_crs& a, const zk_crs& b, const zk_
 
 }  // namespace
 
+void g1_scale_resident(zk_ctx* ctx, hipStream_t st, const G1A* d_in, G1A* d_out, size_t count, const Fr& k_canonical) {
+    g1_scale(ctx, st, d_in, d_out, count, k_canonical);
+}
+
 void g1_scale_batch(zk_ctx* ctx, const uint64_t* points, const uint64_t* scalar, uint64_t* out, size_t n) {
     ZK_REQUIRE(points && scalar && out, ZK_ERR_ARG, "zk_g1_scale_batch: null pointer");
     Fr k = fr_words(scalar);

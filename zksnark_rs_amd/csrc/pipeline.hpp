@@ -134,6 +134,11 @@ void qc_ensure_w_gate(const zk_qap&, hipStream_t);                 // qap_check.
 size_t basis_max_n();                                              // the largest n crs_lagrange_from_powers takes
 void arb_attach_integer_roots(zk_ctx*, zk_qap&);                    // arbroots.hip: the tree of the roots 1..n for an integer-roots QAP (see prove.hip)
 void crs_lagrange_from_powers_tree(zk_ctx*, zk_crs&, const zk_qap&);   // gbasis.hip: the same arrays by the transposed interpolation tree, O(n log^2 n) point operations
+std::shared_ptr<InterpTree> integer_nodes_tree(zk_ctx*, uint64_t first, size_t count);   // gbasis.hip: the interpolation tree of the nodes first .. first + count - 1
+template <class F> void group_interp_transpose(zk_ctx*, const InterpTree&, const Aff<F>* d_bases, Aff<F>* d_out);   // gbasis.hip: out[k] = sum_i M[i][k] bases[i] over ANY t.n points
+void g2_subgroup_check(zk_ctx*, const G2A* d_pts, size_t n, int* d_flag);   // crs.hip: *d_flag |= 8 when a point lies outside the subgroup of order r
+void g1_scale_resident(zk_ctx*, hipStream_t, const G1A* d_in, G1A* d_out, size_t count, const Fr& k_canonical);   // crs_contribute.hip: k_g1_scale over a resident array (d_out may be d_in); synchronises
+zk_crs* crs_from_powers(zk_ctx*, const zk_qap&, const zk_powers_desc&);   // crs_from_powers.hip
 void crs_lagrange_from_powers(zk_ctx*, zk_crs&, const zk_qap&);   // basis.hip: the Lagrange-basis points of an integer-roots QAP from the powers (once per CRS)
 
 void prove_host(zk_ctx*, const zk_crs&, const zk_qap&, const uint64_t* weights, size_t m, const uint64_t r[4], const uint64_t s[4], uint8_t* proof_out);

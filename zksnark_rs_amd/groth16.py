@@ -68,6 +68,17 @@ def setup(qap, trapdoor=None):
     return SigmaG1(qap.ctx, crs, shared), SigmaG2(qap.ctx, crs, shared)
 
 
+def setup_from_powers(qap, powers):
+    """The CRS of `qap` from a powers-of-tau transcript, with gamma = delta = 1 and no trapdoor (zk_crs_from_powers): what a ceremony
+    starts from instead of setup().  powers: a mapping with tau_g1 (>= 2n-1 points), tau_g2, alpha_tau_g1, beta_tau_g1 (>= n points
+    each) and beta_g2, canonical affine limbs.  Then check_setup(qap, sigma) -- the transcript itself is not checked here -- and one
+    contribute() per party, each verified with check_contribution()."""
+    crs = qap.ctx.crs_from_powers(qap.handle, powers["tau_g1"], powers["tau_g2"], powers["alpha_tau_g1"], powers["beta_tau_g1"],
+                                  powers["beta_g2"])
+    shared = {}
+    return SigmaG1(qap.ctx, crs, shared), SigmaG2(qap.ctx, crs, shared)
+
+
 def prove(qap, sigma, weights, rs=None):
     sigmag1, sigmag2 = sigma
     assert sigmag1.crs is sigmag2.crs, "SigmaG1 / SigmaG2 come from different setups"
