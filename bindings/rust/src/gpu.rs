@@ -60,6 +60,35 @@ pub struct ZkPowersDesc {                                // zk_powers_desc: a po
 pub struct PowersOfTau<'a> {
     pub tau_g1: &'a [u64], pub tau_g2: &'a [u64], pub alpha_tau_g1: &'a [u64], pub beta_tau_g1: &'a [u64], pub beta_g2: &'a [u64; 16],
 }
+#[repr(C)] pub struct ZkPowers { _p: [u8; 0] }            // zk_powers: a transcript resident on the device
+#[repr(C)]
+pub struct ZkPowersOut {                                 // zk_powers_out (same field order, mutable; null = skip)
+    tau_g1: *mut u64, tau_g2: *mut u64, alpha_tau_g1: *mut u64, beta_tau_g1: *mut u64, beta_g2: *mut u64,
+}
+#[repr(C)]
+pub struct ZkPowersCheckResult { pub failed: u32, pub flags: u32 }   // zk_powers_check_result: ZK_POWERS_CHECK_* bits
+pub const ZK_POWERS_CHECK_GENERATORS: u32 = 0x001;
+pub const ZK_POWERS_CHECK_POWERS_G1: u32 = 0x002;
+pub const ZK_POWERS_CHECK_POWERS_G2: u32 = 0x004;
+pub const ZK_POWERS_CHECK_ALPHA: u32 = 0x008;
+pub const ZK_POWERS_CHECK_BETA: u32 = 0x010;
+pub const ZK_POWERS_CHECK_BETA_TWINS: u32 = 0x020;
+pub const ZK_POWERS_CHECK_DEGENERATE: u32 = 0x040;
+pub const ZK_POWERS_CHECK_RECORD: u32 = 0x100;
+pub const ZK_POWERS_CHECK_KNOWLEDGE: u32 = 0x200;
+/// zk_powers_contribution: three ZkCrsContribution records (tau | alpha | beta), 672 bytes
+#[repr(C, align(8))]
+#[derive(Clone, Copy)]
+pub struct ZkPowersContribution(pub [u8; 672]);
+/// The five arrays of a transcript as owned vectors (what PowersOfTau::contribute returns); `view` lends them as a PowersOfTau
+pub struct PowersOfTauOwned {
+    pub tau_g1: Vec<u64>, pub tau_g2: Vec<u64>, pub alpha_tau_g1: Vec<u64>, pub beta_tau_g1: Vec<u64>, pub beta_g2: [u64; 16],
+}
+impl PowersOfTauOwned {
+    pub fn view(&self) -> PowersOfTau {
+        PowersOfTau { tau_g1: &self.tau_g1, tau_g2: &self.tau_g2, alpha_tau_g1: &self.alpha_tau_g1, beta_tau_g1: &self.beta_tau_g1, beta_g2: &self.beta_g2 }
+    }
+}
 #[repr(C)]
 pub struct ZkCrsCheckResult { pub failed: u32, pub flags: u32 }   // zk_crs_check_result: ZK_CRS_CHECK_* bits
 pub const ZK_CRS_CHECK_T_ZERO: u32 = 1;                // flags: x is a root of t (consistent, unsound)
@@ -162,6 +191,23 @@ extern "C" {
     fn zk_crs_contribution_verify(c: *const ZkCrsContribution, tag: *const u8, ok: *mut c_int) -> c_int;
     fn zk_crs_contribution_check(ctx: *mut ZkCtx, before: *const ZkCrs, after: *const ZkCrs, c: *const ZkCrsContribution, tag: *const u8,
                                  challenge: *const u64, out: *mut ZkCrsContributionResult) -> c_int;
+    // phase 1: a resident powers-of-tau transcript, its check, a contribution (secrets = null: drawn from the OS, wiped) and the
+    // check of a contribution; the per-point multiplication kernel behind it on chosen scalars
+    fn zk_powers_upload(ctx: *mut ZkCtx, desc: *const ZkPowersDesc, out: *mut *mut ZkPowers) -> c_int;
+    fn zk_powers_initial(ctx: *mut ZkCtx, n_tau_g1: usize, n_rest: usize, out: *mut *mut ZkPowers) -> c_int;
+    fn zk_powers_dims(powers: *const ZkPowers, n_tau_g1: *mut usize, n_rest: *mut usize) -> c_int;
+    fn zk_powers_download(ctx: *mut ZkCtx, powers: *const ZkPowers, out: *const ZkPowersOut) -> c_int;
+    fn zk_powers_free(powers: *mut ZkPowers);
+    fn zk_powers_check(ctx: *mut ZkCtx, powers: *const ZkPowers, challenge: *const u64, out: *mut ZkPowersCheckResult) -> c_int;
+    fn zk_powers_contribution_prove(before: *const u64, secrets: *const u64, nonces: *const u64, tag: *const u8,
+                                    out: *mut ZkPowersContribution) -> c_int;
+    fn zk_powers_contribution_verify(c: *const ZkPowersContribution, tag: *const u8, ok: *mut c_int) -> c_int;
+    fn zk_powers_contribute(ctx: *mut ZkCtx, before: *const ZkPowers, secrets: *const u64, tag: *const u8, out: *mut *mut ZkPowers,
+                            record: *mut ZkPowersContribution) -> c_int;
+    fn zk_powers_contribution_check(ctx: *mut ZkCtx, before: *const ZkPowers, after: *const ZkPowers, record: *const ZkPowersContribution,
+                                    tag: *const u8, challenge: *const u64, out: *mut ZkPowersCheckResult) -> c_int;
+    fn zk_g1_mul_each(ctx: *mut ZkCtx, points: *const u64, scalars: *const u64, out: *mut u64, n: usize) -> c_int;
+    fn zk_g2_mul_each(ctx: *mut ZkCtx, points: *const u64, scalars: *const u64, out: *mut u64, n: usize) -> c_int;
     // a stream of proofs: witnesses in page-locked host memory, two tickets in flight
     fn zk_host_alloc(bytes: usize, out: *mut *mut c_void) -> c_int;
     fn zk_host_free(p: *mut c_void);
@@ -454,6 +500,84 @@ impl Ctx {
     }
 }
 impl Drop for Ctx { fn drop(&mut self) { unsafe { zk_ctx_destroy(self.0) } } }
+
+// ------------------------------------------------------------------------------------------------
+// Phase 1: a powers-of-tau transcript on the device for the length of one call
+// ------------------------------------------------------------------------------------------------
+struct ResidentPowers<'c> { ctx: &'c Ctx, p: *mut ZkPowers }
+impl<'c> Drop for ResidentPowers<'c> { fn drop(&mut self) { unsafe { zk_powers_free(self.p) } } }
+impl<'c> ResidentPowers<'c> {
+    fn upload(ctx: &'c Ctx, t: &PowersOfTau) -> ResidentPowers<'c> {
+        let n_rest = t.tau_g2.len() / 16;
+        assert!(t.tau_g1.len() % 8 == 0 && t.tau_g2.len() % 16 == 0, "a G1 point is 8 words, a G2 point 16");
+        assert!(t.alpha_tau_g1.len() == 8 * n_rest && t.beta_tau_g1.len() == 8 * n_rest, "tau_g2, alpha_tau_g1, beta_tau_g1 differ in length");
+        let desc = ZkPowersDesc { n_tau_g1: t.tau_g1.len() / 8, n_rest, tau_g1: t.tau_g1.as_ptr(), tau_g2: t.tau_g2.as_ptr(),
+                                  alpha_tau_g1: t.alpha_tau_g1.as_ptr(), beta_tau_g1: t.beta_tau_g1.as_ptr(), beta_g2: t.beta_g2.as_ptr() };
+        let mut p: *mut ZkPowers = std::ptr::null_mut();
+        check(ctx.0, unsafe { zk_powers_upload(ctx.0, &desc, &mut p) });
+        ResidentPowers { ctx, p }
+    }
+    fn download(&self) -> PowersOfTauOwned {
+        let (mut n1, mut n2) = (0usize, 0usize);
+        check(self.ctx.0, unsafe { zk_powers_dims(self.p, &mut n1, &mut n2) });
+        let mut t = PowersOfTauOwned { tau_g1: vec![0; 8 * n1], tau_g2: vec![0; 16 * n2], alpha_tau_g1: vec![0; 8 * n2], beta_tau_g1: vec![0; 8 * n2],
+                                       beta_g2: [0; 16] };
+        let out = ZkPowersOut { tau_g1: t.tau_g1.as_mut_ptr(), tau_g2: t.tau_g2.as_mut_ptr(), alpha_tau_g1: t.alpha_tau_g1.as_mut_ptr(),
+                                beta_tau_g1: t.beta_tau_g1.as_mut_ptr(), beta_g2: t.beta_g2.as_mut_ptr() };
+        check(self.ctx.0, unsafe { zk_powers_download(self.ctx.0, self.p, &out) });
+        t
+    }
+}
+impl<'a> PowersOfTau<'a> {
+    /// The head of a ceremony (zk_powers_initial): x = alpha = beta = 1, every entry a generator.
+    pub fn initial(n_tau_g1: usize, n_rest: usize) -> PowersOfTauOwned {
+        let ctx = Ctx::new();
+        let mut p: *mut ZkPowers = std::ptr::null_mut();
+        check(ctx.0, unsafe { zk_powers_initial(ctx.0, n_tau_g1, n_rest, &mut p) });
+        ResidentPowers { ctx: &ctx, p }.download()
+    }
+    /// Is this a powers-of-tau sequence over the library's generators (zk_powers_check; the challenge is drawn from the OS inside the
+    /// library)?  -> the failed ZK_POWERS_CHECK_* bits, 0 = a transcript.  Once per transcript, whatever the circuit.
+    pub fn check(&self) -> u32 {
+        let ctx = Ctx::new();
+        let r = ResidentPowers::upload(&ctx, self);
+        let mut res = ZkPowersCheckResult { failed: 0, flags: 0 };
+        check(ctx.0, unsafe { zk_powers_check(ctx.0, r.p, std::ptr::null(), &mut res) });
+        res.failed
+    }
+    /// Adds the caller's randomness (zk_powers_contribute): the transcript of (alpha a, beta b, x s) for secrets drawn from the OS
+    /// inside the library, wiped and never returned, and the record that proves knowledge of them for `tag`.  The result is checked
+    /// against this transcript before it is returned; a failure there is a bug and panics.
+    pub fn contribute(&self, tag: &[u8; 32]) -> (PowersOfTauOwned, ZkPowersContribution) {
+        let ctx = Ctx::new();
+        let before = ResidentPowers::upload(&ctx, self);
+        let mut rec = ZkPowersContribution([0u8; 672]);
+        let mut next: *mut ZkPowers = std::ptr::null_mut();
+        let mut res = ZkPowersCheckResult { failed: 0, flags: 0 };
+        check(ctx.0, unsafe { zk_powers_contribute(ctx.0, before.p, std::ptr::null(), tag.as_ptr(), &mut next, &mut rec) });
+        let after = ResidentPowers { ctx: &ctx, p: next };
+        check(ctx.0, unsafe { zk_powers_contribution_check(ctx.0, before.p, after.p, &rec, tag.as_ptr(), std::ptr::null(), &mut res) });
+        assert!(res.failed == 0, "zk_powers_contribute made a transcript its own check refuses: {:#x}", res.failed);
+        (after.download(), rec)
+    }
+    /// Is this transcript `before` re-keyed by whoever made `record` for `tag`, and a transcript in its own right
+    /// (zk_powers_contribution_check)?  -> the failed bits, 0 = a valid successor.  `before` is not checked again.
+    pub fn check_contribution(&self, before: &PowersOfTau, record: &ZkPowersContribution, tag: &[u8; 32]) -> u32 {
+        let ctx = Ctx::new();
+        let (old, new) = (ResidentPowers::upload(&ctx, before), ResidentPowers::upload(&ctx, self));
+        let mut res = ZkPowersCheckResult { failed: 0, flags: 0 };
+        check(ctx.0, unsafe { zk_powers_contribution_check(ctx.0, old.p, new.p, record, tag.as_ptr(), std::ptr::null(), &mut res) });
+        res.failed
+    }
+}
+impl ZkPowersContribution {
+    /// zk_powers_contribution_verify (host code, no GPU): do the three parts verify under their role tags for `tag`?
+    pub fn verify(&self, tag: &[u8; 32]) -> bool {
+        let mut ok: c_int = 0;
+        assert_eq!(unsafe { zk_powers_contribution_verify(self, tag.as_ptr(), &mut ok) }, 0, "zk_powers_contribution_verify failed");
+        ok != 0
+    }
+}
 
 fn upload_dense(ctx: &Ctx, qap: &QAP<CoefficientPoly<FrLocal>>) -> *mut ZkQap {
     let (m, n) = (qap.u.len(), qap.degree);

@@ -145,6 +145,15 @@ int zk_g2_mul_batch(zk_ctx* ctx, const uint64_t* points, const uint64_t* scalars
  * once, every lane walks the same digits, and a lane's four points share one field inversion.  Points are expected on the curve (as
  * every CRS array is); for other input the output is unspecified. */
 int zk_g1_scale_batch(zk_ctx* ctx, const uint64_t* points, const uint64_t scalar[4], uint64_t* out, size_t n);
+/* out[i] = scalars[i] * points[i] through the kernel zk_powers_contribute multiplies a transcript with (k_mul_each, csrc/powers.hip,
+ * DESIGN 4n), so that it can be tested on chosen scalars.  Same contract as zk_g1_mul_batch / zk_g2_mul_batch: canonical in and out,
+ * ZK_ERR_RANGE for a scalar >= r or a coordinate >= q, scalar 0 gives infinity, infinity stays infinity, out may be points.  Points
+ * are expected in the group of order r.  The option "powers_mul_form" (zk_set_option; 0 = k_mul_each, the default; 1 = a plain
+ * kernel over gb_mul, the per-lane non-adjacent form) selects the kernel for these calls and for zk_powers_contribute;
+ * "powers_mul_ppl" (0 = chosen from the array's length, the default; 1, 2, 4) fixes how many points a lane of k_mul_each owns and
+ * inverts together -- the results do not depend on either. */
+int zk_g1_mul_each(zk_ctx* ctx, const uint64_t* points, const uint64_t* scalars, uint64_t* out, size_t n);
+int zk_g2_mul_each(zk_ctx* ctx, const uint64_t* points, const uint64_t* scalars, uint64_t* out, size_t n);
 /* out[i] = a[i] + b[i]  (Add for G1Local/G2Local, fr.rs:175-215) */
 int zk_g1_add_batch(zk_ctx* ctx, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n);
 int zk_g2_add_batch(zk_ctx* ctx, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n);
@@ -497,7 +506,8 @@ int zk_crs_contribution_check(zk_ctx* ctx, const zk_crs* before, const zk_crs* a
  * beyond the first 2n - 1 of tau_g1 and the first n of the other arrays are ignored.
  * The call does NOT check that the arrays are a powers-of-tau sequence (tau_g1[k+1] = x tau_g1[k], the same x in G2, alpha and beta
  * the same in every entry): run zk_crs_check(result, qap), which covers every array derived here (POWERS_G1, POWERS_G2, TWINS, XI_T,
- * WIRES, LAGRANGE), before anyone contributes to or proves with the result.
+ * WIRES, LAGRANGE), before anyone contributes to or proves with the result -- or check the transcript itself, once for all circuits
+ * and over every power it holds, with zk_powers_check below.
  *  - Synchronous, on a stream of its own; an outstanding zk_prove_submit ticket is not disturbed.  The new CRS has no window tables:
  *    its first proof builds them, as after zk_crs_upload.
  *  - ZK_ERR_ARG: a null pointer (arrays of the desc included), a QAP of another context, n_tau_g1 < 2n - 1, n_rest < n.
@@ -513,6 +523,102 @@ typedef struct {
     const uint64_t* beta_g2;       /* [beta]_2 */
 } zk_powers_desc;
 int zk_crs_from_powers(zk_ctx* ctx, const zk_qap* qap, const zk_powers_desc* powers, zk_crs** out);
+
+/* Phase 1: the transcript itself (bellman's `powersoftau`, `snarkjs powersoftau contribute` / `verify`).  zk_crs_from_powers takes
+ * whatever arrays it is given; the calls below check a universal transcript ONCE (not per circuit, and over every power, used or not),
+ * add a party's own randomness to it, and check that others did so knowingly -- so that x, alpha and beta are known to nobody as long
+ * as one contributor of the chain was honest.  A zk_powers is the five arrays of zk_powers_desc resident on the device (affine,
+ * Montgomery form, as the arrays of a CRS).
+ *  - zk_powers_upload: the range, curve and G2-subgroup checks and statuses of zk_crs_from_powers; n_rest >= 2 and n_tau_g1 >= n_rest
+ *    (anything else: ZK_ERR_ARG).  Infinity entries are accepted here; zk_powers_check flags them.
+ *  - zk_powers_initial: the head of a ceremony, x = alpha = beta = 1: every G1 entry is the library's generator G (xi_g1[0] of any
+ *    zk_setup CRS), every G2 entry and beta_g2 its generator H.
+ *  - zk_powers_download: canonical affine words into caller buffers, any pointer may be NULL (as zk_crs_download).  The arrays can be
+ *    handed to zk_crs_from_powers as a zk_powers_desc.
+ * On every failure of upload / initial *out is NULL. */
+typedef struct zk_powers zk_powers;
+typedef struct {
+    uint64_t *tau_g1, *tau_g2, *alpha_tau_g1, *beta_tau_g1, *beta_g2;
+} zk_powers_out;
+int zk_powers_upload(zk_ctx* ctx, const zk_powers_desc* desc, zk_powers** out);
+int zk_powers_initial(zk_ctx* ctx, size_t n_tau_g1, size_t n_rest, zk_powers** out);
+int zk_powers_dims(const zk_powers* powers, size_t* n_tau_g1, size_t* n_rest);
+int zk_powers_download(zk_ctx* ctx, const zk_powers* powers, const zk_powers_out* out);
+void zk_powers_free(zk_powers* powers);
+
+/* Are these arrays a powers-of-tau transcript?  A bit of out->failed per relation that does not hold.  G = tau_g1[0], H = tau_g2[0],
+ * N1 = n_tau_g1, N2 = n_rest, rho_k = c^k for the challenge c:
+ *   GENERATORS   G and H are the library's generators.
+ *   POWERS_G1    P = sum_{k<=N1-2} rho_k tau_g1[k], Q = sum_{k<=N1-2} rho_k tau_g1[k+1]:  e(P, tau_g2[1]) = e(Q, H).
+ *   POWERS_G2    e(sum_{k<N2} rho_k tau_g1[k], H) = e(G, S2),  S2 = sum_{k<N2} rho_k tau_g2[k]  (one G2 sum for this and the next two).
+ *   ALPHA        e(sum_{k<N2} rho_k alpha_tau_g1[k], H) = e(alpha_tau_g1[0], S2).
+ *   BETA         the same over beta_tau_g1.
+ *   BETA_TWINS   e(beta_tau_g1[0], H) = e(G, beta_g2).
+ *   DEGENERATE   tau_g1[1], tau_g2[1], alpha_tau_g1[0], beta_tau_g1[0] or beta_g2 is infinity (x, alpha or beta is 0).
+ * With GENERATORS, POWERS_G1 says tau_g1[k] = x^k G for the x of tau_g2[1]; POWERS_G2 carries the same x^k to tau_g2; ALPHA and BETA
+ * say the entries are alpha x^k, beta x^k for ONE alpha, ONE beta.  The sums go through the MSM launcher over one-off tables on a
+ * stream of the call's own (freed before return); about a dozen pairings on the host.  The handle is read only; synchronous; an
+ * outstanding zk_prove_submit ticket is not disturbed.
+ * Soundness: each relation is a polynomial identity in c of degree below N1, so a transcript that violates one passes with
+ * probability below N1 / r over a challenge its maker could not predict.  NULL draws 256 bits from the OS; a fixed challenge is for
+ * tests ONLY.
+ * ZK_ERR_ARG: a null pointer (challenge excepted), a handle of another context, challenge = 0.  ZK_ERR_RANGE: challenge >= r.  On every
+ * error *out is untouched. */
+#define ZK_POWERS_CHECK_GENERATORS 0x001u
+#define ZK_POWERS_CHECK_POWERS_G1 0x002u
+#define ZK_POWERS_CHECK_POWERS_G2 0x004u
+#define ZK_POWERS_CHECK_ALPHA 0x008u
+#define ZK_POWERS_CHECK_BETA 0x010u
+#define ZK_POWERS_CHECK_BETA_TWINS 0x020u
+#define ZK_POWERS_CHECK_DEGENERATE 0x040u
+#define ZK_POWERS_CHECK_RECORD 0x100u      /* zk_powers_contribution_check only */
+#define ZK_POWERS_CHECK_KNOWLEDGE 0x200u   /* zk_powers_contribution_check only */
+typedef struct {
+    uint32_t failed;
+    uint32_t flags;    /* reserved, 0 */
+} zk_powers_check_result;
+int zk_powers_check(zk_ctx* ctx, const zk_powers* powers, const uint64_t challenge[4] /* NULL = OS */, zk_powers_check_result* out);
+
+/* A contribution: the transcript of (alpha a, beta b, x s) from the transcript of (alpha, beta, x), for secrets s, a, b of the
+ * caller's -- byte for byte the arrays a transcript built from those three products holds:
+ *   tau_g1[k] *= s^k (k < N1), tau_g2[k] *= s^k, alpha_tau_g1[k] *= a s^k, beta_tau_g1[k] *= b s^k (k < N2), beta_g2 *= b.
+ * Every point takes a DIFFERENT scalar: the scalars are made and kept on the device (canonical), and k_mul_each (csrc/powers.hip)
+ * multiplies one point per lane with an instruction stream that is the same for every lane of a wave: endomorphism split, regular
+ * signed windows (every digit non-zero), a per-point table of odd multiples in LDS, one constant-time inversion per four points.
+ *  - secrets: s, a, b as 3 x 4 canonical words, each 1 <= v < r; NULL draws all three from the OS -- they are then never returned.
+ *    The device scalar arrays and every host copy are wiped before the call returns.  0: ZK_ERR_DIV_BY_ZERO; >= r: ZK_ERR_RANGE.
+ *    (1, 1, 1) gives an equal transcript.
+ *  - `before` is read only; synchronous, on a stream of its own.  ZK_ERR_ARG: a null pointer (secrets and tag excepted), a handle of
+ *    another context.  On every failure *out is NULL and *record is untouched.  A degenerate `before` (an infinity among tau_g1[1],
+ *    alpha_tau_g1[0], beta_tau_g1[0]) is multiplied like any other -- infinities stay infinities -- but no proof of knowledge exists
+ *    over an infinity: that part of the record is all zero and never verifies.
+ * The record holds three of the Schnorr records of zk_crs_contribution_prove, one per secret:
+ *   tau    knowledge of s with tau_g1[1]' = s tau_g1[1];   alpha   of a with alpha_tau_g1[0]' = a alpha_tau_g1[0];
+ *   beta   of b with beta_tau_g1[0]' = b beta_tau_g1[0]
+ * each bound to tag_role = SHA-256("ZKPOWv1\0" | role byte (1 tau, 2 alpha, 3 beta) | tag) (tag NULL = 32 zero bytes), so that a
+ * record cannot stand in another role or another ceremony step.  Nonces come from the OS.  zk_powers_contribution_prove is the host
+ * side alone (no context): `before` = the three before-points (8 words each: tau_g1[1], alpha_tau_g1[0], beta_tau_g1[0]); fixed
+ * nonces (3 x 4 words) are for tests ONLY.  zk_powers_contribution_verify: *ok = 1 iff all three verify under their role tags. */
+typedef struct {
+    zk_crs_contribution tau, alpha, beta;
+} zk_powers_contribution;
+int zk_powers_contribution_prove(const uint64_t before[24], const uint64_t secrets[12], const uint64_t nonces[12] /* NULL = OS */,
+                                 const uint8_t tag[32], zk_powers_contribution* out);
+int zk_powers_contribution_verify(const zk_powers_contribution* c, const uint8_t tag[32], int* ok);
+int zk_powers_contribute(zk_ctx* ctx, const zk_powers* before, const uint64_t secrets[12] /* s, a, b; NULL = OS */, const uint8_t tag[32],
+                         zk_powers** out, zk_powers_contribution* record);
+
+/* Is `after` a transcript, and is it `before` re-keyed by someone who knew the factors?  out->failed carries the ZK_POWERS_CHECK_* bits
+ * of zk_powers_check(after), and
+ *   RECORD       the six points of the record are not tau_g1[1], alpha_tau_g1[0], beta_tau_g1[0] of the two transcripts;
+ *   KNOWLEDGE    one of the three zk_crs_contribution_verify calls, under its role tag, fails;
+ *   DEGENERATE   (also) an after-point of the record is infinity.
+ * `before` is NOT checked again: the head of a chain is zk_powers_initial or one zk_powers_check, and every later link is this call
+ * (failed == 0 says `after` is a transcript in its own right, and the record ties its x, alpha, beta to those of `before`).
+ * Soundness and the challenge as for zk_powers_check.  ZK_ERR_ARG: a null pointer (tag and challenge excepted), transcripts of
+ * different dims or another context, challenge = 0; ZK_ERR_RANGE: challenge >= r.  On every error *out is untouched. */
+int zk_powers_contribution_check(zk_ctx* ctx, const zk_powers* before, const zk_powers* after, const zk_powers_contribution* record,
+                                 const uint8_t tag[32], const uint64_t challenge[4] /* NULL = OS */, zk_powers_check_result* out);
 
 /* On-disk CRS container. The reference has no serialisation of SigmaG1/SigmaG2
  * (groth16/mod.rs:105-121), and setup (mod.rs:134-197) draws a fresh trapdoor on every call, so a CRS must be

@@ -60,9 +60,17 @@ int zk_profile_entry(const zk_ctx* ctx, int i, const char** name, double* total_
  *                      |k2| (2 words), k = k1 + k2 lambda mod r; raw_out: ZK_GLV_RECODE_WORDS per scalar: k1 < 0, k2 < 0, the top
  *                      digit position (-1 for k = 0), then ZK_GLV_RECODE_DIGITS signed digits of k1 and as many of k2 (position i
  *                      weighs 2^i; the half's sign is folded into its digits) */
+/* The scalar side of k_mul_each (csrc/mul_each_recode.hpp: the split with nearest rounding and the REGULAR signed fixed-window
+ * recoding every lane does for its own scalar; the same functions compiled for the host), likewise: HOST code, ctx may be NULL,
+ * b / c / d ignored; field selects the group whose window width W is used (0 = G1, 1 = G2).
+ *   ZK_LAZY_REGULAR_RECODE a, out: as ZK_LAZY_GLV_RECODE; raw_out: ZK_REGULAR_RECODE_WORDS per scalar: k1 < 0, k2 < 0, |k1| even,
+ *                      |k2| even (the half was recoded as its magnitude + 1), the digit count ND, then ZK_REGULAR_RECODE_DIGITS slots
+ *                      for the digits of k1 and as many for k2, of which the first ND are used (position i weighs 2^(W i); every
+ *                      digit odd, |digit| < 2^W; they recompose to the MAGNITUDE, plus one where it is even -- the sign is separate) */
 enum { ZK_LAZY_MONT = 0, ZK_LAZY_SQR = 1, ZK_LAZY_MONT_DIFF = 2, ZK_LAZY_NORM = 3, ZK_LAZY_STORE = 4, ZK_LAZY_FR_REDUCE = 5, ZK_LAZY_FR_STORE = 6,
-       ZK_LAZY_FP2_MUL = 7, ZK_LAZY_FP2_SQR = 8, ZK_LAZY_GLV_RECODE = 9 };
+       ZK_LAZY_FP2_MUL = 7, ZK_LAZY_FP2_SQR = 8, ZK_LAZY_GLV_RECODE = 9, ZK_LAZY_REGULAR_RECODE = 10 };
 enum { ZK_GLV_RECODE_DIGITS = 132, ZK_GLV_RECODE_WORDS = 3 + 2 * 132 };
+enum { ZK_REGULAR_RECODE_DIGITS = 48, ZK_REGULAR_RECODE_WORDS = 5 + 2 * 48 };
 int zk_lazy29_batch(zk_ctx* ctx, int field, int op, const int32_t* a, const int32_t* b, const int32_t* c, const int32_t* d, size_t n,
                     uint64_t* out, int32_t* raw_out);
 

@@ -431,6 +431,108 @@ inline ContributionCheck check_contribution(const Context& c, const Sigma& befor
     return ContributionCheck{r.failed};
 }
 
+// Phase 1 (zk_powers_*): the transcript itself, resident on the device.  check_powers: is it a powers-of-tau sequence over the
+// library's generators (once per transcript, whatever the circuit)?  contribute_powers: the transcript of (alpha a, beta b, x s) for
+// secrets drawn from the OS inside the library (wiped, never returned; contribute_powers_with fixes them, for tests) and the record
+// that proves knowledge of them for a tag.  check_powers_contribution: is `after` a transcript, and `before` re-keyed by whoever made
+// the record?  `before` is not checked again: a chain starts at ResidentPowers::initial or one check_powers.  download() gives the
+// PowersOfTau that setup_from_powers takes.
+struct PowersCheck {
+    uint32_t failed = 0;   // ZK_POWERS_CHECK_GENERATORS .. ZK_POWERS_CHECK_KNOWLEDGE: the relations that do not hold
+    bool ok() const { return failed == 0; }
+    bool has(uint32_t bit) const { return (failed & bit) != 0; }
+};
+using PowersContributionCheck = PowersCheck;
+struct PowersContribution {
+    zk_powers_contribution raw{};
+    bool verify(const Tag& tag) const {   // zk_powers_contribution_verify: host code, no context
+        int ok = 0;
+        const int st = zk_powers_contribution_verify(&raw, tag.data(), &ok);
+        if (st != ZK_OK) throw Error(st, "PowersContribution::verify");
+        return ok != 0;
+    }
+};
+class ResidentPowers {
+   public:
+    ResidentPowers(ResidentPowers&& o) noexcept : p_(std::exchange(o.p_, nullptr)) {}
+    ResidentPowers(const ResidentPowers&) = delete;
+    ~ResidentPowers() { if (p_) zk_powers_free(p_); }
+    const zk_powers* get() const { return p_; }
+    static ResidentPowers upload(const Context& c, const PowersOfTau& p) {
+        if (p.tau_g1.size() % ZK_G1_WORDS || p.tau_g2.size() % ZK_G2_WORDS || p.alpha_tau_g1.size() * 2 != p.tau_g2.size() ||
+            p.beta_tau_g1.size() * 2 != p.tau_g2.size())
+            throw Error(ZK_ERR_ARG, "ResidentPowers::upload: tau_g2, alpha_tau_g1 and beta_tau_g1 must hold the same number of whole points");
+        zk_powers_desc d{p.tau_g1.size() / ZK_G1_WORDS, p.tau_g2.size() / ZK_G2_WORDS, p.tau_g1.data(), p.tau_g2.data(), p.alpha_tau_g1.data(),
+                         p.beta_tau_g1.data(), p.beta_g2.data()};
+        zk_powers* h = nullptr;
+        c.check(zk_powers_upload(c.get(), &d, &h), "ResidentPowers::upload");
+        return ResidentPowers(h);
+    }
+    static ResidentPowers initial(const Context& c, size_t n_tau_g1, size_t n_rest) {
+        zk_powers* h = nullptr;
+        c.check(zk_powers_initial(c.get(), n_tau_g1, n_rest, &h), "ResidentPowers::initial");
+        return ResidentPowers(h);
+    }
+    std::pair<size_t, size_t> dims() const {
+        size_t n1 = 0, n2 = 0;
+        zk_powers_dims(p_, &n1, &n2);
+        return {n1, n2};
+    }
+    PowersOfTau download(const Context& c) const {
+        const auto d = dims();
+        PowersOfTau p;
+        p.tau_g1.resize(d.first * ZK_G1_WORDS); p.tau_g2.resize(d.second * ZK_G2_WORDS);
+        p.alpha_tau_g1.resize(d.second * ZK_G1_WORDS); p.beta_tau_g1.resize(d.second * ZK_G1_WORDS);
+        const zk_powers_out o{p.tau_g1.data(), p.tau_g2.data(), p.alpha_tau_g1.data(), p.beta_tau_g1.data(), p.beta_g2.data()};
+        c.check(zk_powers_download(c.get(), p_, &o), "ResidentPowers::download");
+        return p;
+    }
+
+   private:
+    friend std::pair<ResidentPowers, PowersContribution> contribute_powers_with(const Context&, const ResidentPowers&, const std::array<FrLocal, 3>&, const Tag&);
+    friend std::pair<ResidentPowers, PowersContribution> contribute_powers(const Context&, const ResidentPowers&, const Tag&);
+    explicit ResidentPowers(zk_powers* p) : p_(p) {}
+    zk_powers* p_;
+};
+inline PowersCheck check_powers_with(const Context& c, const ResidentPowers& p, const FrLocal& challenge) {
+    zk_powers_check_result r{};
+    c.check(zk_powers_check(c.get(), p.get(), challenge.w.data(), &r), "groth16::check_powers");
+    return PowersCheck{r.failed};
+}
+inline PowersCheck check_powers(const Context& c, const ResidentPowers& p) {
+    zk_powers_check_result r{};
+    c.check(zk_powers_check(c.get(), p.get(), nullptr, &r), "groth16::check_powers");
+    return PowersCheck{r.failed};
+}
+inline std::pair<ResidentPowers, PowersContribution> contribute_powers_with(const Context& c, const ResidentPowers& p, const std::array<FrLocal, 3>& sab,
+                                                                            const Tag& tag) {
+    uint64_t sec[12];
+    for (int k = 0; k < 3; ++k)
+        for (int l = 0; l < 4; ++l) sec[4 * k + l] = sab[k].w[l];
+    zk_powers* h = nullptr;
+    PowersContribution rec;
+    c.check(zk_powers_contribute(c.get(), p.get(), sec, tag.data(), &h, &rec.raw), "groth16::contribute_powers");
+    return {ResidentPowers(h), rec};
+}
+inline std::pair<ResidentPowers, PowersContribution> contribute_powers(const Context& c, const ResidentPowers& p, const Tag& tag) {
+    zk_powers* h = nullptr;
+    PowersContribution rec;
+    c.check(zk_powers_contribute(c.get(), p.get(), nullptr, tag.data(), &h, &rec.raw), "groth16::contribute_powers");
+    return {ResidentPowers(h), rec};
+}
+inline PowersContributionCheck check_powers_contribution_with(const Context& c, const ResidentPowers& before, const ResidentPowers& after,
+                                                              const PowersContribution& rec, const Tag& tag, const FrLocal& challenge) {
+    zk_powers_check_result r{};
+    c.check(zk_powers_contribution_check(c.get(), before.get(), after.get(), &rec.raw, tag.data(), challenge.w.data(), &r), "groth16::check_powers_contribution");
+    return PowersCheck{r.failed};
+}
+inline PowersContributionCheck check_powers_contribution(const Context& c, const ResidentPowers& before, const ResidentPowers& after,
+                                                         const PowersContribution& rec, const Tag& tag) {
+    zk_powers_check_result r{};
+    c.check(zk_powers_contribution_check(c.get(), before.get(), after.get(), &rec.raw, tag.data(), nullptr, &r), "groth16::check_powers_contribution");
+    return PowersCheck{r.failed};
+}
+
 // groth16::verify((sigma_g1, sigma_g2), &inputs, proof) (mod.rs:299-320)
 inline bool verify(const Context& c, const Sigma& sigma, const std::vector<FrLocal>& inputs, const Proof& proof) {
     int ok = 0;

@@ -25,7 +25,8 @@ Q_MODULUS = 21888242871839275222246405745257275088696311157297823662689037894645
 
 __all__ = ["Context", "ZkError", "fr_to_limbs", "limbs_to_int", "ints_to_limbs", "limbs_to_ints",
            "PROOF_BYTES", "PARTIAL_BYTES", "MAX_IN_FLIGHT", "MAX_BATCH", "R_MODULUS", "Q_MODULUS", "SplitMix64", "pairing", "proof_save", "proof_load",
-           "PROOF_COMPRESSED_BYTES", "proof_compress", "proof_decompress", "VerifyingKey", "CrsCheck"]
+           "PROOF_COMPRESSED_BYTES", "proof_compress", "proof_decompress", "VerifyingKey", "CrsCheck",
+           "Powers", "PowersCheck", "PowersContribution", "PowersContributionCheck", "powers_contribution_prove", "powers_role_tag"]
 
 
 class ZkError(RuntimeError):
@@ -299,6 +300,104 @@ for _k, _n in enumerate(_lib.CONTRIB_BITS):
     setattr(ContributionCheck, _n, 1 << _k)
 
 
+class Powers(_Handle):
+    """Device-resident powers-of-tau transcript (zk_powers): tau_g1 (n_tau_g1 points), tau_g2, alpha_tau_g1, beta_tau_g1 (n_rest points
+    each) and beta_g2.  Context.powers_download(handle) gives the arrays as a dict of canonical affine limbs."""
+    n_tau_g1 = n_rest = 0
+
+
+class PowersCheck:
+    """What zk_powers_check / zk_powers_contribution_check found: `failed` = the ZK_POWERS_CHECK_* bits of the relations that do not
+    hold (class attributes PowersCheck.POWERS_G1, ...); `names` lists them; `ok`: none."""
+
+    def __init__(self, failed, flags=0):
+        self.failed, self.flags = int(failed), int(flags)
+
+    @property
+    def ok(self):
+        return self.failed == 0
+
+    @property
+    def names(self):
+        return [n for k, n in enumerate(_lib.POWERS_CHECK_BITS) if n and self.failed >> k & 1]
+
+    def __repr__(self):
+        return "%s(failed=%s)" % (type(self).__name__, "|".join(self.names) or "0")
+
+
+class PowersContributionCheck(PowersCheck):
+    """zk_powers_contribution_check's answer: PowersCheck's bits for `after`, and RECORD / KNOWLEDGE for the record."""
+
+
+for _k, _n in enumerate(_lib.POWERS_CHECK_BITS):
+    if _n:
+        setattr(PowersCheck, _n, 1 << _k)
+
+
+def _secrets_arg(values, what):
+    """None or three scalars (ints or (4,) limbs) -> (array kept alive, u64 pointer or None)"""
+    if values is None:
+        return None, None
+    if len(values) != 3:
+        raise ValueError("%s: three scalars" % what)
+    return _u64(np.stack([fr_to_limbs(v) if isinstance(v, int) else np.asarray(v, np.uint64).reshape(4) for v in values]))
+
+
+class PowersContribution:
+    """The record of a powers-of-tau contribution (zk_powers_contribution): three Contribution records -- .tau (knowledge of s on
+    tau_g1[1]), .alpha (a on alpha_tau_g1[0]), .beta (b on beta_tau_g1[0]) -- each bound to its role and the caller's tag.
+    to_bytes / from_bytes: the 672-byte memory image."""
+
+    def __init__(self, raw=None):
+        self.raw = raw if raw is not None else _lib.PowersContribution()
+
+    def to_bytes(self):
+        return bytes(bytearray(self.raw))
+
+    @classmethod
+    def from_bytes(cls, data):
+        data = bytes(data)
+        if len(data) != 3 * _lib.CONTRIBUTION_BYTES:
+            raise ValueError("a powers contribution record is %d bytes" % (3 * _lib.CONTRIBUTION_BYTES))
+        return cls(_lib.PowersContribution.from_buffer_copy(data))
+
+    tau = property(lambda self: Contribution.from_bytes(bytes(bytearray(self.raw.tau))))
+    alpha = property(lambda self: Contribution.from_bytes(bytes(bytearray(self.raw.alpha))))
+    beta = property(lambda self: Contribution.from_bytes(bytes(bytearray(self.raw.beta))))
+
+    def verify(self, tag=None):
+        """zk_powers_contribution_verify (host code): do all three parts verify under their role tags for `tag`?"""
+        t, tp = _tag_arg(tag)
+        ok = C.c_int(0)
+        rc = _lib.load().zk_powers_contribution_verify(C.byref(self.raw), tp, C.byref(ok))
+        if rc != 0:
+            raise ZkError(rc)
+        return bool(ok.value)
+
+    def __eq__(self, other):
+        return isinstance(other, PowersContribution) and self.to_bytes() == other.to_bytes()
+
+
+def powers_role_tag(role, tag=None):
+    """SHA-256("ZKPOWv1\\0" | role byte | tag): the tag a part of a PowersContribution is bound to (role 1 tau, 2 alpha, 3 beta)"""
+    import hashlib
+    return hashlib.sha256(b"ZKPOWv1\0" + bytes([role]) + (bytes(tag) if tag is not None else bytes(32))).digest()
+
+
+def powers_contribution_prove(before, secrets, nonces=None, tag=None):
+    """zk_powers_contribution_prove (host code, no Context).  before: the three before-points tau_g1[1], alpha_tau_g1[0],
+    beta_tau_g1[0] as (3, 8) limbs; secrets: (s, a, b); nonces: None = drawn from the OS, three fixed ones are for tests only."""
+    b, bp = _u64(np.asarray(before).reshape(24))
+    s_, sp = _secrets_arg(secrets, "secrets")
+    k_, kp = _secrets_arg(nonces, "nonces")
+    t, tp = _tag_arg(tag)
+    out = PowersContribution()
+    rc = _lib.load().zk_powers_contribution_prove(bp, sp, kp, tp, C.byref(out.raw))
+    if rc != 0:
+        raise ZkError(rc)
+    return out
+
+
 class Context:
     def __init__(self, device=0):
         self.lib = _lib.load()
@@ -395,6 +494,13 @@ class Context:
 
     def g2_mul_batch(self, points, scalars):
         return self._pt2(self.lib.zk_g2_mul_batch, 16, points, scalars, 4)
+
+    def g1_mul_each(self, points, scalars):
+        """zk_g1_mul_each: out[i] = scalars[i] points[i] through k_mul_each, the kernel of powers_contribute (option "powers_mul_form")"""
+        return self._pt2(self.lib.zk_g1_mul_each, 8, points, scalars, 4)
+
+    def g2_mul_each(self, points, scalars):
+        return self._pt2(self.lib.zk_g2_mul_each, 16, points, scalars, 4)
 
     def g1_scale_batch(self, points, scalar):
         """zk_g1_scale_batch: every point times ONE scalar (an int or (4,) limbs) -> (n, 8) array."""
@@ -542,11 +648,81 @@ class Context:
         self._check(self.lib.zk_crs_contribution_check(self.ptr, before.ptr, after.ptr, C.byref(contribution.raw), tp, sp, C.byref(out)))
         return ContributionCheck(out.failed, out.flags)
 
-    def crs_from_powers(self, qap, tau_g1, tau_g2, alpha_tau_g1, beta_tau_g1, beta_g2):
+    # ---- powers of tau (phase 1) ----
+    def _powers(self, p):
+        h = Powers(self, p, self.lib.zk_powers_free)
+        n1, n2 = C.c_size_t(), C.c_size_t()
+        self._check(self.lib.zk_powers_dims(p, C.byref(n1), C.byref(n2)))
+        h.n_tau_g1, h.n_rest = n1.value, n2.value
+        return h
+
+    def powers_upload(self, tau_g1, tau_g2, alpha_tau_g1, beta_tau_g1, beta_g2):
+        """zk_powers_upload: a resident transcript from canonical affine limbs (range, curve and G2-subgroup checked; whether it IS a
+        transcript is powers_check's question).  -> Powers"""
+        t1, t1p = _u64(np.asarray(tau_g1).reshape(-1, 8))
+        t2, t2p = _u64(np.asarray(tau_g2).reshape(-1, 16))
+        a1, a1p = _u64(np.asarray(alpha_tau_g1).reshape(-1, 8))
+        b1, b1p = _u64(np.asarray(beta_tau_g1).reshape(-1, 8))
+        b2, b2p = _u64(np.asarray(beta_g2).reshape(16))
+        if not (t2.shape[0] == a1.shape[0] == b1.shape[0]):
+            raise ValueError("tau_g2, alpha_tau_g1 and beta_tau_g1 differ in length")
+        d = _lib.PowersDesc(t1.shape[0], t2.shape[0], t1p, t2p, a1p, b1p, b2p)
+        p = C.c_void_p()
+        self._check(self.lib.zk_powers_upload(self.ptr, C.byref(d), C.byref(p)))
+        return self._powers(p)
+
+    def powers_initial(self, n_tau_g1, n_rest):
+        """zk_powers_initial: the head of a ceremony (x = alpha = beta = 1: every entry a generator).  -> Powers"""
+        p = C.c_void_p()
+        self._check(self.lib.zk_powers_initial(self.ptr, n_tau_g1, n_rest, C.byref(p)))
+        return self._powers(p)
+
+    def powers_download(self, powers):
+        """zk_powers_download -> dict(tau_g1, tau_g2, alpha_tau_g1, beta_tau_g1, beta_g2) of canonical affine limbs"""
+        n1, n2 = powers.n_tau_g1, powers.n_rest
+        arrs = dict(tau_g1=np.zeros((n1, 8), np.uint64), tau_g2=np.zeros((n2, 16), np.uint64), alpha_tau_g1=np.zeros((n2, 8), np.uint64),
+                    beta_tau_g1=np.zeros((n2, 8), np.uint64), beta_g2=np.zeros(16, np.uint64))
+        out = _lib.PowersOut(*[arrs[k].ctypes.data_as(_lib.u64p) for k in ("tau_g1", "tau_g2", "alpha_tau_g1", "beta_tau_g1", "beta_g2")])
+        self._check(self.lib.zk_powers_download(self.ptr, powers.ptr, C.byref(out)))
+        return arrs
+
+    def powers_check(self, powers, challenge=None):
+        """zk_powers_check: is `powers` a powers-of-tau transcript over the library's generators?  -> PowersCheck.  challenge: None
+        draws it from the OS (the only sound choice); an int in [1, r) or (4,) limbs fixes it, for tests."""
+        s_, sp = _fr_arg(challenge)
+        out = _lib.PowersCheckResult(0xFFFFFFFF, 0xFFFFFFFF)
+        self._check(self.lib.zk_powers_check(self.ptr, powers.ptr, sp, C.byref(out)))
+        return PowersCheck(out.failed, out.flags)
+
+    def powers_contribute(self, powers, secrets=None, tag=None):
+        """zk_powers_contribute: the transcript of (alpha a, beta b, x s) and the record proving knowledge of the three factors for
+        `tag`.  secrets: None draws (s, a, b) from the OS inside the library (wiped, never returned); three ints in [1, r) fix them,
+        for tests.  -> (Powers, PowersContribution)"""
+        s_, sp = _secrets_arg(secrets, "secrets")
+        t, tp = _tag_arg(tag)
+        p = C.c_void_p()
+        rec = PowersContribution()
+        self._check(self.lib.zk_powers_contribute(self.ptr, powers.ptr, sp, tp, C.byref(p), C.byref(rec.raw)))
+        return self._powers(p), rec
+
+    def powers_contribution_check(self, before, after, contribution, tag=None, challenge=None):
+        """zk_powers_contribution_check: is `after` a transcript, and `before` re-keyed by whoever made `contribution` for `tag`?
+        -> PowersContributionCheck.  `before` is not checked again.  Leave `challenge` None outside tests."""
+        s_, sp = _fr_arg(challenge)
+        t, tp = _tag_arg(tag)
+        out = _lib.PowersCheckResult(0xFFFFFFFF, 0xFFFFFFFF)
+        self._check(self.lib.zk_powers_contribution_check(self.ptr, before.ptr, after.ptr, C.byref(contribution.raw), tp, sp, C.byref(out)))
+        return PowersContributionCheck(out.failed, out.flags)
+
+    def crs_from_powers(self, qap, tau_g1, tau_g2=None, alpha_tau_g1=None, beta_tau_g1=None, beta_g2=None):
         """zk_crs_from_powers: the CRS of `qap` (roots-of-unity or integer-roots form) from a powers-of-tau transcript, by group
         operations only -- byte-equal to setup(qap, (alpha, beta, 1, 1, x)) for the transcript's (alpha, beta, x).  tau_g1: (>= 2n-1, 8)
         points [x^k]_1; tau_g2 (>= n, 16), alpha_tau_g1, beta_tau_g1 (>= n, 8) of one common length; beta_g2: (16,).  The transcript is
-        NOT checked to be a sequence of powers: run crs_check(result, qap).  -> Crs"""
+        NOT checked to be a sequence of powers: run crs_check(result, qap), or powers_check on the transcript.  A Powers handle may be
+        given in place of the five arrays: it is downloaded.  -> Crs"""
+        if isinstance(tau_g1, Powers):
+            a = self.powers_download(tau_g1)
+            tau_g1, tau_g2, alpha_tau_g1, beta_tau_g1, beta_g2 = (a[k] for k in ("tau_g1", "tau_g2", "alpha_tau_g1", "beta_tau_g1", "beta_g2"))
         t1, t1p = _u64(np.asarray(tau_g1).reshape(-1, 8))
         t2, t2p = _u64(np.asarray(tau_g2).reshape(-1, 16))
         a1, a1p = _u64(np.asarray(alpha_tau_g1).reshape(-1, 8))

@@ -27,6 +27,10 @@ CRS_CHECK_T_ZERO = 1             # ZK_CRS_CHECK_T_ZERO
 CRS_CHECK_LAGRANGE_PRESENT = 2   # ZK_CRS_CHECK_LAGRANGE_PRESENT
 # zk_crs_contribution_result.failed (ZK_CONTRIB_*), in bit order
 CONTRIB_BITS = ("UNCHANGED", "RECORD", "KNOWLEDGE", "DELTA_TWINS", "SUM_DELTA", "XI_T", "DEGENERATE")
+# zk_powers_check_result.failed, bit k = POWERS_CHECK_BITS[k] (ZK_POWERS_CHECK_*; bit 7 is unused; RECORD and KNOWLEDGE: the contribution check only)
+POWERS_CHECK_BITS = ("GENERATORS", "POWERS_G1", "POWERS_G2", "ALPHA", "BETA", "BETA_TWINS", "DEGENERATE", None, "RECORD", "KNOWLEDGE")
+LAZY_REGULAR_RECODE = 10         # ZK_LAZY_REGULAR_RECODE (include/zkgpu_measure.h)
+REGULAR_RECODE_DIGITS, REGULAR_RECODE_WORDS = 48, 5 + 2 * 48
 CONTRIBUTION_BYTES = 224         # sizeof(zk_crs_contribution): its memory image is its byte form
 
 u64p = C.POINTER(C.c_uint64)
@@ -80,6 +84,18 @@ class CrsContribution(C.Structure):
 
 class CrsContributionResult(C.Structure):
     _fields_ = [("failed", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class PowersOut(C.Structure):
+    _fields_ = [("tau_g1", u64p), ("tau_g2", u64p), ("alpha_tau_g1", u64p), ("beta_tau_g1", u64p), ("beta_g2", u64p)]
+
+
+class PowersCheckResult(C.Structure):
+    _fields_ = [("failed", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class PowersContribution(C.Structure):
+    _fields_ = [("tau", CrsContribution), ("alpha", CrsContribution), ("beta", CrsContribution)]
 
 
 # zk_comm_ops / zk_mgpu_backend: tables of C callbacks (tests plug gloo and CPU stand-ins in here)
@@ -161,6 +177,19 @@ SIGNATURES = {
     "zk_crs_contribution_check": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CrsContribution), u8p, u64p,
                                             C.POINTER(CrsContributionResult)]),
     "zk_crs_from_powers": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(PowersDesc), C.POINTER(C.c_void_p)]),
+    "zk_g1_mul_each": (C.c_int, [C.c_void_p, u64p, u64p, u64p, C.c_size_t]),
+    "zk_g2_mul_each": (C.c_int, [C.c_void_p, u64p, u64p, u64p, C.c_size_t]),
+    "zk_powers_upload": (C.c_int, [C.c_void_p, C.POINTER(PowersDesc), C.POINTER(C.c_void_p)]),
+    "zk_powers_initial": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_void_p)]),
+    "zk_powers_dims": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "zk_powers_download": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(PowersOut)]),
+    "zk_powers_free": (None, [C.c_void_p]),
+    "zk_powers_check": (C.c_int, [C.c_void_p, C.c_void_p, u64p, C.POINTER(PowersCheckResult)]),
+    "zk_powers_contribution_prove": (C.c_int, [u64p, u64p, u64p, u8p, C.POINTER(PowersContribution)]),
+    "zk_powers_contribution_verify": (C.c_int, [C.POINTER(PowersContribution), u8p, C.POINTER(C.c_int)]),
+    "zk_powers_contribute": (C.c_int, [C.c_void_p, C.c_void_p, u64p, u8p, C.POINTER(C.c_void_p), C.POINTER(PowersContribution)]),
+    "zk_powers_contribution_check": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PowersContribution), u8p, u64p,
+                                               C.POINTER(PowersCheckResult)]),
     "zk_crs_dims": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "zk_crs_download": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(CrsOut)]),
     "zk_crs_free": (None, [C.c_void_p]),

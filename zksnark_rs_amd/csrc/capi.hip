@@ -8,6 +8,7 @@
 #include "pipeline.hpp"
 #include "interp.hpp"
 #include "crs_contribution.hpp"
+#include "mul_each_recode.hpp"
 
 using namespace zk;
 
@@ -139,6 +140,8 @@ static long* option_slot(zk_ctx* ctx, const char* key) {
     if (!std::strcmp(key, "interp_large_log")) return &ctx->opt_interp_large_log;
     if (!std::strcmp(key, "comm_cu_reserve")) return &ctx->opt_comm_cu_reserve;
     if (!std::strcmp(key, "basis_tree_min")) return &ctx->opt_basis_tree_min;
+    if (!std::strcmp(key, "powers_mul_form")) return &ctx->opt_powers_mul_form;
+    if (!std::strcmp(key, "powers_mul_ppl")) return &ctx->opt_powers_mul_ppl;
     if (!std::strcmp(key, "merge_lh")) return &ctx->opt_merge_lh;
     if (!std::strcmp(key, "witgen_scratch_kib")) return &ctx->opt_witgen_scratch_kib;
     if (!std::strcmp(key, "vk_table_kib")) return &ctx->opt_vk_table_kib;
@@ -243,6 +246,45 @@ int zk_lazy29_batch(zk_ctx* ctx, int field, int op, const int32_t* a, const int3
                 int32_t* r = raw_out + (size_t)ZK_GLV_RECODE_WORDS * e;
                 r[0] = n1; r[1] = n2; r[2] = dg.top;
                 for (int i = 0; i < ZK_GLV_RECODE_DIGITS; ++i) { r[3 + i] = dg.d1[i]; r[3 + ZK_GLV_RECODE_DIGITS + i] = dg.d2[i]; }
+            }
+        });
+    }
+    if (op == ZK_LAZY_REGULAR_RECODE) {   // host code, no context: the split and the regular recoding a lane of k_mul_each does (zkgpu_measure.h)
+        if (!a || !out || !raw_out || field < 0 || field > 1) return ZK_ERR_ARG;
+        return guarded(nullptr, [&] {
+            for (size_t e = 0; e < n; ++e) {
+                const uint32_t* k = reinterpret_cast<const uint32_t*>(a) + 8 * e;
+                uint32_t k1[5], k2[5];
+                bool n1, n2, e1, e2;
+                glv_split_nearest(k, k1, n1, k2, n2);
+                ZK_REQUIRE(k1[4] == 0 && k2[4] == 0, ZK_ERR_SIZE, "glv_split_nearest: a half of 2^128 or more");
+                out[4 * e] = k1[0] | ((uint64_t)k1[1] << 32); out[4 * e + 1] = k1[2] | ((uint64_t)k1[3] << 32);
+                out[4 * e + 2] = k2[0] | ((uint64_t)k2[1] << 32); out[4 * e + 3] = k2[2] | ((uint64_t)k2[3] << 32);
+                int32_t* r = raw_out + (size_t)ZK_REGULAR_RECODE_WORDS * e;
+                for (int i = 0; i < ZK_REGULAR_RECODE_WORDS; ++i) r[i] = 0;
+                auto digits = [&](auto width, const uint32_t* m, bool& even, int32_t* dst) {
+                    constexpr int W = decltype(width)::value;
+                    typedef RegularRecode<W> RR;
+                    uint32_t b[RR::NW];
+                    regular_recode<W>(m, b, even);
+                    for (int i = RR::ND - 1; i >= 0; --i) {   // most significant first
+                        uint32_t index;
+                        bool negative;
+                        regular_next<W>(b, index, negative);
+                        dst[i] = negative ? -(int32_t)(2 * index + 1) : (int32_t)(2 * index + 1);
+                    }
+                    for (int i = 0; i < RR::NW; ++i) ZK_REQUIRE(b[i] == 0, ZK_ERR_SIZE, "regular_recode: bits left after the last digit");
+                    return RR::ND;
+                };
+                int nd;
+                if (field == 0) {
+                    nd = digits(std::integral_constant<int, ME_W_G1>(), k1, e1, r + 5);
+                    digits(std::integral_constant<int, ME_W_G1>(), k2, e2, r + 5 + ZK_REGULAR_RECODE_DIGITS);
+                } else {
+                    nd = digits(std::integral_constant<int, ME_W_G2>(), k1, e1, r + 5);
+                    digits(std::integral_constant<int, ME_W_G2>(), k2, e2, r + 5 + ZK_REGULAR_RECODE_DIGITS);
+                }
+                r[0] = n1; r[1] = n2; r[2] = e1; r[3] = e2; r[4] = nd;
             }
         });
     }

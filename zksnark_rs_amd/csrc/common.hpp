@@ -148,6 +148,8 @@ struct zk_ctx {
     long opt_run_entries = 32;    // longest run of the bucket accumulation when buckets are cut into several runs (multiple of 4)
     long opt_run_fill = 1;        // products cut into several runs per bucket: runs as long as one round of accumulation lanes allows (fewer merges)
     long opt_run_whole = 128;     // products with at most this many entries per bucket (and enough buckets) keep every bucket in ONE run
+    long opt_powers_mul_form = 0;     // zk_powers_contribute, zk_g*_mul_each: 0 = k_mul_each (regular windows, the same instruction stream in every lane), 1 = a plain kernel over gb_mul (per-lane non-adjacent form): the comparator of tools/time_powers.py (powers.hip)
+    long opt_powers_mul_ppl = 0;      // k_mul_each: points a lane owns; 0 = chosen from the array's length (4 once the array fills the machine for two rounds of waves, else 2 or 1), 1 / 2 / 4 = fixed (the tests run every value at every length)
     long opt_basis_tree_min = 16384; // integer-roots QAP over a powers-only CRS: from this many gates on the Lagrange-basis points come from the transposed interpolation tree (gbasis.hip), below from the n^2 inner products (basis.hip)
     long opt_interp_large_log = 20; // interp.hip: trees of at least 2^this elements per level take the form that halves the upward transforms
     long opt_quad_buckets = 65536; // inner products of at most this many buckets run their reduction tail with four lanes per addition (msm_quad.hpp)

@@ -24,4 +24,10 @@ bool contribution_prove(const uint64_t delta_before[8], const Fr& d_can, const F
 bool contribution_verify(const zk_crs_contribution& c, const uint8_t tag[32]);
 Fr draw_scalar_nonzero();   // 256 bits from the OS reduced mod r, never 0 (canonical)
 
+// powers_record.hip: the three records of a powers-of-tau contribution under their role tags (host code)
+void powers_role_tag(int role, const uint8_t tag[32], uint8_t out[32]);
+int powers_contribution_prove(const uint64_t before[24], const uint64_t secrets[12], const uint64_t* nonces, const uint8_t tag[32],
+                              zk_powers_contribution* out);   // a status; *out untouched unless ZK_OK
+bool powers_contribution_verify(const zk_powers_contribution&, const uint8_t tag[32]);
+
 }  // namespace zk

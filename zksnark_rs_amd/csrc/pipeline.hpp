@@ -94,7 +94,25 @@ struct zk_crs {
     long tables_c = -1;      // the msm_window_bits option the tables were built for
 };
 
+// a powers-of-tau transcript (powers.hip): the arrays of zk_powers_desc, affine Montgomery
+struct zk_powers {
+    zk_ctx* ctx = nullptr;
+    size_t n1 = 0, n2 = 0;                          // n_tau_g1, n_rest
+    zk::DevBuf<zk::G1A> tau1, alpha_tau1, beta_tau1;
+    zk::DevBuf<zk::G2A> tau2, beta2;
+};
+
 namespace zk {
+
+// powers.hip
+zk_powers* powers_upload(zk_ctx*, const zk_powers_desc&);
+zk_powers* powers_initial(zk_ctx*, size_t n1, size_t n2);
+void powers_download(zk_ctx*, const zk_powers&, const zk_powers_out&);
+void powers_check(zk_ctx*, const zk_powers&, const uint64_t* challenge, zk_powers_check_result* out);
+zk_powers* powers_contribute(zk_ctx*, const zk_powers&, const uint64_t* secrets, const uint8_t* tag, zk_powers_contribution* record);
+void powers_contribution_check(zk_ctx*, const zk_powers& before, const zk_powers& after, const zk_powers_contribution&, const uint8_t* tag,
+                               const uint64_t* challenge, zk_powers_check_result* out);
+template <class F> void mul_each_batch(zk_ctx*, const uint64_t* points, const uint64_t* scalars, uint64_t* out, size_t n);
 
 zk_qap* qap_upload_sparse(zk_ctx*, const zk_qap_sparse_desc&);
 zk_qap* qap_upload_rows(zk_ctx*, const zk_qap_sparse_desc&, size_t n);                  // rows over n gates, domain not set

@@ -71,12 +71,35 @@ def setup(qap, trapdoor=None):
 def setup_from_powers(qap, powers):
     """The CRS of `qap` from a powers-of-tau transcript, with gamma = delta = 1 and no trapdoor (zk_crs_from_powers): what a ceremony
     starts from instead of setup().  powers: a mapping with tau_g1 (>= 2n-1 points), tau_g2, alpha_tau_g1, beta_tau_g1 (>= n points
-    each) and beta_g2, canonical affine limbs.  Then check_setup(qap, sigma) -- the transcript itself is not checked here -- and one
+    each) and beta_g2, canonical affine limbs, or a resident Powers handle (check_powers / contribute_powers: it is downloaded).  Then
+    check_setup(qap, sigma) -- the transcript itself is not checked here, that is check_powers -- and one
     contribute() per party, each verified with check_contribution()."""
-    crs = qap.ctx.crs_from_powers(qap.handle, powers["tau_g1"], powers["tau_g2"], powers["alpha_tau_g1"], powers["beta_tau_g1"],
-                                  powers["beta_g2"])
+    if hasattr(powers, "ptr"):   # a resident Powers handle: downloaded by crs_from_powers
+        crs = qap.ctx.crs_from_powers(qap.handle, powers)
+    else:
+        crs = qap.ctx.crs_from_powers(qap.handle, powers["tau_g1"], powers["tau_g2"], powers["alpha_tau_g1"], powers["beta_tau_g1"],
+                                      powers["beta_g2"])
     shared = {}
     return SigmaG1(qap.ctx, crs, shared), SigmaG2(qap.ctx, crs, shared)
+
+
+def check_powers(powers, challenge=None):
+    """Is the resident transcript `powers` a powers-of-tau sequence over the library's generators (zk_powers_check)?  Once per
+    transcript, whatever the circuit.  -> PowersCheck: .ok, .failed, .names.  Leave `challenge` None outside tests."""
+    return powers.ctx.powers_check(powers, challenge)
+
+
+def contribute_powers(powers, secrets=None, tag=None):
+    """Add one's own randomness to a transcript: the transcript of (alpha a, beta b, x s) and the PowersContribution that proves
+    knowledge of (s, a, b) for `tag` (zk_powers_contribute).  Leave `secrets` None (drawn inside the library, wiped, never
+    returned) outside tests."""
+    return powers.ctx.powers_contribute(powers, secrets, tag)
+
+
+def check_powers_contribution(before, after, contribution, tag=None, challenge=None):
+    """Is `after` a transcript, and `before` re-keyed by whoever made `contribution` for `tag` (zk_powers_contribution_check)?  The
+    head of a chain is Context.powers_initial or one check_powers.  -> PowersContributionCheck."""
+    return before.ctx.powers_contribution_check(before, after, contribution, tag, challenge)
 
 
 def prove(qap, sigma, weights, rs=None):
