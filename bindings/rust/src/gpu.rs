@@ -176,6 +176,31 @@ extern "C" {
     fn zk_witgen_create(ctx: *mut ZkCtx, c: *const ZkCircuit, out: *mut *mut ZkWitgen) -> c_int;
     fn zk_witgen_free(w: *mut ZkWitgen);
     fn zk_witgen_run(w: *mut ZkWitgen, d_inputs: *const c_void, n_in: usize, count: usize, d_weights_out: *mut c_void, m: usize) -> c_int;
+    // the gate-level circuit builder (circuit/builder/mod.rs) behind the ABI, and bit-sliced witnesses of boolean built circuits
+    fn zk_builder_create(out: *mut *mut ZkBuilder) -> c_int;
+    fn zk_builder_free(b: *mut ZkBuilder);
+    fn zk_builder_last_error(b: *const ZkBuilder) -> *const c_char;
+    fn zk_builder_dims(b: *const ZkBuilder, wires: *mut usize, gates: *mut usize) -> c_int;
+    fn zk_builder_new_wires(b: *mut ZkBuilder, kind: c_int, count: usize, out: *mut u32) -> c_int;
+    fn zk_builder_sub_circuit(b: *mut ZkBuilder, left_weights: *const u64, left_wires: *const u32, nl: usize, right_weights: *const u64,
+                              right_wires: *const u32, nr: usize, out: *mut u32) -> c_int;
+    fn zk_builder_gate(b: *mut ZkBuilder, kind: c_int, x: u32, y: u32, out: *mut u32) -> c_int;
+    fn zk_builder_bitwise(b: *mut ZkBuilder, kind: c_int, x: *const u32, y: *const u32, n: usize, out: *mut u32) -> c_int;
+    fn zk_builder_fan_in(b: *mut ZkBuilder, kind: c_int, x: *const u32, n: usize, out: *mut u32) -> c_int;
+    fn zk_builder_compare(b: *mut ZkBuilder, kind: c_int, left: *const u32, right: *const u32, n_bits: usize, out: *mut u32) -> c_int;
+    fn zk_builder_keccak(b: *mut ZkBuilder, in_wires: *const u32, n_bytes: usize, rate_bytes: c_uint, delim: c_uint, rounds: c_uint,
+                         out_wires: *mut u32, out_bytes: usize) -> c_int;
+    fn zk_builder_assert_bit(b: *mut ZkBuilder, wire: u32) -> c_int;
+    fn zk_builder_finish(b: *mut ZkBuilder, verify_wires: *const u32, n_verify: usize, out: *mut *mut ZkCircuit) -> c_int;
+    fn zk_circuit_is_boolean(c: *const ZkCircuit) -> c_int;
+    fn zk_circuit_wire_index(c: *const ZkCircuit, wire: u32, index: *mut usize) -> c_int;
+    fn zk_circuit_qap_sparse_unity(ctx: *mut ZkCtx, c: *const ZkCircuit, out: *mut *mut ZkQap) -> c_int;
+    fn zk_boolgen_create(ctx: *mut ZkCtx, c: *const ZkCircuit, out: *mut *mut ZkBoolgen) -> c_int;
+    fn zk_boolgen_free(g: *mut ZkBoolgen);
+    fn zk_boolgen_run(g: *mut ZkBoolgen, d_in_bits: *const c_void, in_stride_bytes: usize, count: usize, d_weights_out: *mut c_void,
+                      m: usize) -> c_int;
+    fn zk_boolgen_eval(g: *mut ZkBoolgen, d_in_bits: *const c_void, in_stride_bytes: usize, count: usize, wires: *const u32, n_wires: usize,
+                       d_out_bits: *mut c_void, out_stride_bytes: usize) -> c_int;
     // does a witness satisfy the QAP (sparse forms)?  One witness on the host, or `count` of them where zk_witgen_run left them
     fn zk_qap_check(ctx: *mut ZkCtx, qap: *const ZkQap, weights: *const u64, m: usize, out: *mut ZkQapCheckResult) -> c_int;
     fn zk_qap_check_dev(ctx: *mut ZkCtx, qap: *const ZkQap, d_weights: *const c_void, m: usize, stride: usize, count: usize,
@@ -230,6 +255,8 @@ extern "C" {
 #[repr(C)] pub struct ZkComm { _p: [u8; 0] }
 #[repr(C)] pub struct ZkCircuit { _p: [u8; 0] }
 #[repr(C)] pub struct ZkWitgen { _p: [u8; 0] }
+#[repr(C)] pub struct ZkBuilder { _p: [u8; 0] }
+#[repr(C)] pub struct ZkBoolgen { _p: [u8; 0] }
 #[repr(C)] pub struct ZkMgpu { _p: [u8; 0] }
 
 fn check(ctx: *mut ZkCtx, rc: c_int) {
@@ -1178,6 +1205,147 @@ pub fn verify<P>(sigma: (&SigmaG1<G1Local>, &SigmaG2<G2Local>), inputs: &[FrLoca
         zk_crs_free(crs);
     }
     ok == 1
+}
+
+// ------------------------------------------------------------------------------------------------
+// The gate-level builder and bit-sliced witnesses.  Like the rest of this file written without a toolchain: the extern block above
+// is held against include/zkgpu.h by tests/test_abi.py, the wrappers below have never been compiled.  The crate's own
+// circuit::builder::Circuit<T> keeps its place for CPU evaluation; this one produces what the GPU prover takes.
+// ------------------------------------------------------------------------------------------------
+pub type WireId = u32;                       // 0 = the constant zero, 1 = the constant one (builder/mod.rs:91-114)
+#[derive(Clone, Copy)]
+pub enum Gate { BitChecker = 0, Not = 1, And = 2, Or = 3, Xor = 4, Nand = 5, Nor = 6, Xnor = 7, LessThan = 8, GreaterThan = 9 }
+#[derive(Clone, Copy)]
+pub enum Comparator { IsEqual = 0, IsEqualZero = 1, LessThan = 2, LessThanEq = 3, GreaterThan = 4, GreaterThanEq = 5 }
+
+pub struct GpuCircuitBuilder(*mut ZkBuilder);
+/// what zk_builder_finish returns: rows, witness order and both tapes (an ordinary zk_circuit)
+pub struct BuiltCircuit(*mut ZkCircuit);
+impl Drop for GpuCircuitBuilder { fn drop(&mut self) { unsafe { zk_builder_free(self.0) } } }
+impl Drop for BuiltCircuit { fn drop(&mut self) { unsafe { zk_circuit_free(self.0) } } }
+
+impl GpuCircuitBuilder {
+    pub fn new() -> Self {
+        let mut b: *mut ZkBuilder = std::ptr::null_mut();
+        assert_eq!(unsafe { zk_builder_create(&mut b) }, 0);
+        GpuCircuitBuilder(b)
+    }
+    fn ok(&self, rc: c_int) {
+        // the reference's builder panics (expect / assert!) where this one refuses
+        if rc != 0 { panic!("{}", unsafe { std::ffi::CStr::from_ptr(zk_builder_last_error(self.0)) }.to_string_lossy()) }
+    }
+    pub fn zero_wire(&self) -> WireId { 0 }
+    pub fn unity_wire(&self) -> WireId { 1 }
+    fn new_wires(&mut self, kind: c_int, count: usize) -> Vec<WireId> {
+        let mut out = vec![0u32; count];
+        self.ok(unsafe { zk_builder_new_wires(self.0, kind, count, out.as_mut_ptr()) });
+        out
+    }
+    pub fn new_wire(&mut self) -> WireId { self.new_wires(1, 1)[0] }          // any field element: the circuit is not boolean
+    pub fn new_word8(&mut self) -> Vec<WireId> { self.new_wires(0, 8) }       // least significant bit first
+    pub fn new_word64(&mut self) -> Vec<WireId> { self.new_wires(0, 64) }
+    pub fn const_word8(&self, x: u8) -> Vec<WireId> { (0..8).map(|i| ((x >> i) & 1) as u32).collect() }
+    pub fn const_word64(&self, x: u64) -> Vec<WireId> { (0..64).map(|i| ((x >> i) & 1) as u32).collect() }
+    pub fn new_sub_circuit(&mut self, lhs: &[(FrLocal, WireId)], rhs: &[(FrLocal, WireId)]) -> WireId {
+        let (lw, rw): (Vec<FrLocal>, Vec<FrLocal>) = (lhs.iter().map(|t| t.0).collect(), rhs.iter().map(|t| t.0).collect());
+        let (li, ri): (Vec<u32>, Vec<u32>) = (lhs.iter().map(|t| t.1).collect(), rhs.iter().map(|t| t.1).collect());
+        let mut out = 0u32;
+        self.ok(unsafe { zk_builder_sub_circuit(self.0, frs(&lw).as_ptr(), li.as_ptr(), li.len(), frs(&rw).as_ptr(), ri.as_ptr(), ri.len(), &mut out) });
+        out
+    }
+    pub fn gate(&mut self, g: Gate, x: WireId, y: WireId) -> WireId {
+        let mut out = 0u32;
+        self.ok(unsafe { zk_builder_gate(self.0, g as c_int, x, y, &mut out) });
+        out
+    }
+    pub fn new_not(&mut self, x: WireId) -> WireId { self.gate(Gate::Not, x, 0) }
+    pub fn new_and(&mut self, x: WireId, y: WireId) -> WireId { self.gate(Gate::And, x, y) }
+    pub fn new_or(&mut self, x: WireId, y: WireId) -> WireId { self.gate(Gate::Or, x, y) }
+    pub fn new_xor(&mut self, x: WireId, y: WireId) -> WireId { self.gate(Gate::Xor, x, y) }
+    pub fn new_nand(&mut self, x: WireId, y: WireId) -> WireId { self.gate(Gate::Nand, x, y) }
+    pub fn new_nor(&mut self, x: WireId, y: WireId) -> WireId { self.gate(Gate::Nor, x, y) }
+    pub fn new_xnor(&mut self, x: WireId, y: WireId) -> WireId { self.gate(Gate::Xnor, x, y) }
+    pub fn assert_bit(&mut self, w: WireId) { self.ok(unsafe { zk_builder_assert_bit(self.0, w) }) }
+    pub fn fan_in(&mut self, inputs: &[WireId], g: Gate) -> WireId {
+        let mut out = 0u32;
+        self.ok(unsafe { zk_builder_fan_in(self.0, g as c_int, inputs.as_ptr(), inputs.len(), &mut out) });
+        out
+    }
+    /// u8_bitwise_op / u64_bitwise_op / bitwise_op: element-wise over two arrays of one length
+    pub fn bitwise_op(&mut self, left: &[WireId], right: &[WireId], g: Gate) -> Vec<WireId> {
+        assert!(left.len() == right.len());
+        let mut out = vec![0u32; left.len()];
+        self.ok(unsafe { zk_builder_bitwise(self.0, g as c_int, left.as_ptr(), right.as_ptr(), left.len(), out.as_mut_ptr()) });
+        out
+    }
+    /// is_equal .. greater_than_eq (mod.rs:995-1241); IsEqualZero ignores `right`
+    pub fn compare(&mut self, kind: Comparator, left: &[WireId], right: &[WireId]) -> WireId {
+        let mut out = 0u32;
+        let r = if let Comparator::IsEqualZero = kind { std::ptr::null() } else { assert!(left.len() == right.len()); right.as_ptr() };
+        self.ok(unsafe { zk_builder_compare(self.0, kind as c_int, left.as_ptr(), r, left.len(), &mut out) });
+        out
+    }
+    /// the sponge in general form; `input` holds 8 wires per byte
+    pub fn keccak(&mut self, input: &[WireId], rate: u32, delim: u8, rounds: u32, out_bytes: usize) -> Vec<WireId> {
+        assert!(input.len() % 8 == 0);
+        let mut out = vec![0u32; 8 * out_bytes];
+        self.ok(unsafe { zk_builder_keccak(self.0, input.as_ptr(), input.len() / 8, rate as c_uint, delim as c_uint, rounds as c_uint, out.as_mut_ptr(), out_bytes) });
+        out
+    }
+    pub fn keccak256(&mut self, input: &[WireId]) -> Vec<WireId> { self.keccak(input, 136, 0x01, 24, 32) }
+    pub fn keccak256_stream(&mut self, input: &[WireId]) -> Vec<WireId> { self.keccak256(input) }
+    /// ValidateOrder (mod.rs:1459-1476): (is_x_within_range, is_y_greater_than_c, hash_x_y)
+    pub fn validate_order(&mut self, x: &[WireId], range: (&[WireId], &[WireId]), y: &[WireId], c: &[WireId]) -> (WireId, WireId, Vec<WireId>) {
+        let x_geq = self.compare(Comparator::GreaterThanEq, x, range.0);
+        let x_leq = self.compare(Comparator::LessThanEq, x, range.1);
+        let in_range = self.new_and(x_geq, x_leq);
+        let y_geq = self.compare(Comparator::GreaterThanEq, y, c);
+        let stream: Vec<WireId> = x.iter().chain(y.iter()).cloned().collect();
+        (in_range, y_geq, self.keccak256_stream(&stream))
+    }
+    pub fn finish(&mut self, verify: &[WireId]) -> BuiltCircuit {
+        let mut c: *mut ZkCircuit = std::ptr::null_mut();
+        self.ok(unsafe { zk_builder_finish(self.0, verify.as_ptr(), verify.len(), &mut c) });
+        BuiltCircuit(c)
+    }
+}
+
+impl BuiltCircuit {
+    pub fn is_boolean(&self) -> bool { unsafe { zk_circuit_is_boolean(self.0) == 1 } }
+    pub fn wire_index(&self, wire: WireId) -> Option<usize> {
+        let mut i = 0usize;
+        if unsafe { zk_circuit_wire_index(self.0, wire, &mut i) } == 0 { Some(i) } else { None }
+    }
+    /// (m, n, input, n_in)
+    pub fn dims(&self) -> (usize, usize, usize, usize) {
+        let (mut m, mut n, mut l, mut k) = (0usize, 0usize, 0usize, 0usize);
+        unsafe { zk_circuit_dims(self.0, &mut m, &mut n, &mut l, &mut k) };
+        (m, n, l, k)
+    }
+    /// the rows at the roots of unity (zk_circuit_qap_sparse_unity); free with zk_qap_free
+    pub fn qap_sparse_unity(&self, ctx: *mut ZkCtx) -> *mut ZkQap {
+        let mut q: *mut ZkQap = std::ptr::null_mut();
+        unsafe { check(ctx, zk_circuit_qap_sparse_unity(ctx, self.0, &mut q)) };
+        q
+    }
+}
+
+/// zk_boolgen_*: witnesses of a boolean built circuit for `count` packed input rows, left in device memory where the batched prover
+/// takes them (d_weights_out + j * m * 32 bytes is witness j)
+pub struct Boolgen { ctx: *mut ZkCtx, g: *mut ZkBoolgen, m: usize }
+impl Drop for Boolgen { fn drop(&mut self) { unsafe { zk_boolgen_free(self.g) } } }
+impl Boolgen {
+    pub fn new(ctx: *mut ZkCtx, circuit: &BuiltCircuit) -> Self {
+        let mut g: *mut ZkBoolgen = std::ptr::null_mut();
+        unsafe { check(ctx, zk_boolgen_create(ctx, circuit.0, &mut g)) };
+        Boolgen { ctx, g, m: circuit.dims().0 }
+    }
+    pub fn run(&self, d_in_bits: *const c_void, in_stride_bytes: usize, count: usize, d_weights_out: *mut c_void) {
+        unsafe { check(self.ctx, zk_boolgen_run(self.g, d_in_bits, in_stride_bytes, count, d_weights_out, self.m)) }
+    }
+    pub fn eval(&self, d_in_bits: *const c_void, in_stride_bytes: usize, count: usize, wires: &[u32], d_out_bits: *mut c_void, out_stride_bytes: usize) {
+        unsafe { check(self.ctx, zk_boolgen_eval(self.g, d_in_bits, in_stride_bytes, count, wires.as_ptr(), wires.len(), d_out_bits, out_stride_bytes)) }
+    }
 }
 
 // ------------------------------------------------------------------------------------------------

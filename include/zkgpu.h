@@ -93,7 +93,8 @@ const char* zk_last_error(const zk_ctx* ctx);          /* detail of the last fai
  * product L = sum a_i sum_delta_i and H + r B1 + s A, which only occur added together in the proof element c, are ONE inner product
  * over the table xi_t | xi | sum_delta with one set of buckets and one reduction tail; 0 = two products as in round 4; same proof
  * bytes, +1.3 % proofs/s at 2^20 gates, profiles/r5_experiments.txt item 2), "witgen_scratch_kib" (read by zk_witgen_create: how much
- * device memory, in KiB, that generator may hold for slot values; default 8388608 = 8 GiB), "qap_check_chunk" and
+ * device memory, in KiB, that generator may hold for slot values; default 8388608 = 8 GiB), "boolgen_scratch_kib",
+ * "boolgen_group_words" and "boolgen_expand_form" (see zk_boolgen_run), "qap_check_chunk" and
  * "qap_check_by_instance" (see zk_qap_check), "vk_table_kib" (see zk_vk_verify_batch).  Each is exercised by a -m gpu test.  Unknown keys are
  * answered with ZK_ERR_UNSUPPORTED.  Measurement entry points and switches -- kernel event timing, the tuning keys of bench.py --opt /
  * --serialize -- are NOT part of this header: include/zkgpu_measure.h. */
@@ -317,6 +318,116 @@ void zk_witgen_free(zk_witgen* w);     /* NULL is a no-op */
  * "witgen_scratch_kib" -- `count` is not limited by memory (the instances run in chunks), a program of which 64 instances do not fit
  * gives ZK_ERR_SIZE. */
 int zk_witgen_run(zk_witgen* w, const void* d_inputs, size_t n_in, size_t count, void* d_weights_out, size_t m);
+
+/* ------------------------------------------------------------------------------------------
+ * Gate-level circuit builder (the reference's second front end: circuit/builder/mod.rs, types.rs; host code, no context)
+ * ---------------------------------------------------------------------------------------- */
+/* Circuit<T> (builder/mod.rs:56-64).  Wires are numbered from 2 in creation order; wire 0 is the constant 0 and wire 1 the constant 1
+ * (Circuit::new, zero_wire, unity_wire: mod.rs:91-114).  Every call below returns ZK_ERR_ARG with text (zk_builder_last_error) for a
+ * wire id that was never handed out and for any call but zk_builder_free after zk_builder_finish.
+ * Deviations from the reference, all deliberate:
+ *   - wire and witness order are deterministic (creation order; the reference iterates a HashMap);
+ *   - the constant-zero wire is NOT a witness wire: a wire meant to be 0 that no constraint fixes would let the prover put anything
+ *     there, so its entries are dropped from every sub-circuit at zk_builder_finish (they contribute 0 either way);
+ *   - the reference's builder -> DummyRep conversion prepends num_wires empty rows and is not reproduced: sub-circuit k
+ *     is gate k;
+ *   - zk_builder_assert_bit exists (see there). */
+typedef struct zk_builder zk_builder;
+#define ZK_WIRE_ZERO 0u
+#define ZK_WIRE_ONE 1u
+#define ZK_WIRE_BIT 0     /* an input that must be 0 or 1: new_word8 / new_word64 are 8 / 64 of them, least significant bit first (mod.rs:151-190) */
+#define ZK_WIRE_FIELD 1   /* an input that is any field element (new_wire, mod.rs:120-125); the circuit is then not boolean */
+int zk_builder_create(zk_builder** out);
+void zk_builder_free(zk_builder* b);     /* NULL is a no-op */
+const char* zk_builder_last_error(const zk_builder* b);
+/* wires handed out so far (the two constants included) and sub-circuits = gates so far; either pointer may be NULL */
+int zk_builder_dims(const zk_builder* b, size_t* wires, size_t* gates);
+/* `count` new input wires, ids to out[0..count).  The circuit's inputs are these wires in creation order. */
+int zk_builder_new_wires(zk_builder* b, int kind, size_t count, uint32_t* out);
+/* new_sub_circuit (mod.rs:491-557): (sum left_weights[i] * left_wires[i]) * (sum right_weights[i] * right_wires[i]) = *out, a new wire.
+ * Weights are 4 canonical words each (>= r: ZK_ERR_RANGE).  The circuit is then not boolean. */
+int zk_builder_sub_circuit(zk_builder* b, const uint64_t* left_weights, const uint32_t* left_wires, size_t nl, const uint64_t* right_weights,
+                           const uint32_t* right_wires, size_t nr, uint32_t* out);
+/* new_bit_checker, new_not, new_and, new_or, new_xor, new_nand, new_nor, new_xnor (mod.rs:723-798), new_less_than, new_greater_than
+ * (mod.rs:939-950): exactly the reference's sub-circuits with its weights -- OR, NAND and NOR are two, the intermediate AND wire
+ * included -- and no constant folding: a gate on ZK_WIRE_ZERO or ZK_WIRE_ONE is still a gate.  y is ignored by BIT_CHECK and NOT.
+ * The bit checker's output x (x - 1) is an ordinary, unconstrained wire, as in the reference. */
+#define ZK_GATE_BIT_CHECK 0
+#define ZK_GATE_NOT 1
+#define ZK_GATE_AND 2
+#define ZK_GATE_OR 3
+#define ZK_GATE_XOR 4
+#define ZK_GATE_NAND 5
+#define ZK_GATE_NOR 6
+#define ZK_GATE_XNOR 7
+#define ZK_GATE_LESS 8
+#define ZK_GATE_GREATER 9
+int zk_builder_gate(zk_builder* b, int kind, uint32_t x, uint32_t y, uint32_t* out);
+/* bitwise_op (mod.rs:817-827): out[i] = gate(x[i], y[i]), i ascending; y may be NULL for the unary kinds */
+int zk_builder_bitwise(zk_builder* b, int kind, const uint32_t* x, const uint32_t* y, size_t n, uint32_t* out);
+/* fan_in (mod.rs:801-814): the left fold gate(.. gate(gate(x[0], x[1]), x[2]) .., x[n-1]); n >= 1, n == 1 emits nothing; binary kinds only */
+int zk_builder_fan_in(zk_builder* b, int kind, const uint32_t* x, size_t n, uint32_t* out);
+/* is_equal, is_equal_zero, less_than, less_than_eq, greater_than, greater_than_eq (mod.rs:995-1241) over two arrays of n_bits >= 1 bit
+ * wires, least significant first, in the reference's composition.  EQUAL_ZERO ignores `right`.  At n_bits == 1 the reference's
+ * greater_than panics (a fan_in over no equalities); here it is the single new_greater_than gate. */
+#define ZK_CMP_EQUAL 0
+#define ZK_CMP_EQUAL_ZERO 1
+#define ZK_CMP_LESS 2
+#define ZK_CMP_LESS_EQ 3
+#define ZK_CMP_GREATER 4
+#define ZK_CMP_GREATER_EQ 5
+int zk_builder_compare(zk_builder* b, int kind, const uint32_t* left, const uint32_t* right, size_t n_bits, uint32_t* out);
+/* The sponge of keccakf_1600 / absorb / xorin / pad / squeeze (mod.rs:1247-1398) in general form: in_wires are 8 * n_bytes bit wires
+ * (byte k = wires 8k .. 8k+7, least significant first), out_wires receives 8 * out_bytes.  Absorb is XOR into the state, the padding
+ * XORs `delim` at the offset and 0x80 at rate_bytes - 1; theta is 5 x 5 XORs from the zero word and a 3-input XOR fan-in, rho / pi
+ * rename, chi is NOT, AND, XOR, iota XORs a constant word.  keccak256 (mod.rs:1428-1439) is (136, 0x01, 24), SHA3-256 (136, 0x06, 24).
+ * rounds in 1..24 runs the first `rounds` rounds of the permutation (short forms for tests and demonstrations): 9664 gates per round,
+ * 8 k + 16 + 9664 rounds for a one-block message of k bytes.  rate_bytes in 1..200. */
+int zk_builder_keccak(zk_builder* b, const uint32_t* in_wires, size_t n_bytes, unsigned rate_bytes, unsigned delim, unsigned rounds,
+                      uint32_t* out_wires, size_t out_bytes);
+/* The gate w (w - 1) = 0 with NO output wire (an empty W entry).  The reference's bit checker only produces an unconstrained wire,
+ * so without this call a verifier has no way to force an input to be 0 or 1. */
+int zk_builder_assert_bit(zk_builder* b, uint32_t wire);
+/* The circuit as an ordinary zk_circuit (free it with zk_circuit_free; the builder may be freed before or after).  Witness order: the
+ * constant 1, the verify wires in the order given (qap.input = n_verify), the remaining input wires in creation order, the remaining
+ * wires by id.  Sub-circuit k is gate k (0-based), at root k + 1 of zk_circuit_qap / _qap_sparse.  ZK_ERR_ARG with text: a verify wire
+ * named twice or equal to a constant.  Every zk_circuit_* call and zk_witgen_create work on the result: zk_circuit_weights evaluates
+ * the sub-circuits in creation order (what the reference's memoised evaluate, mod.rs:559-595, computes), zk_circuit_weights_tape and
+ * zk_witgen_run a tape compiled from them; n_in is the number of input wires, inputs are field elements in creation order, and a
+ * value other than 0 or 1 on a ZK_WIRE_BIT input is ZK_ERR_RANGE with instance, input and wire named. */
+int zk_builder_finish(zk_builder* b, const uint32_t* verify_wires, size_t n_verify, zk_circuit** out);
+/* 1: every input is a bit wire and every sub-circuit came from a gate, a comparator, the sponge or zk_builder_assert_bit, so
+ * zk_boolgen_create takes the circuit; 0: anything else, every parsed circuit included */
+int zk_circuit_is_boolean(const zk_circuit* c);
+/* witness index of a builder wire in a built circuit (ZK_WIRE_ONE -> 0).  ZK_ERR_ARG: a parsed circuit, an unknown id, ZK_WIRE_ZERO. */
+int zk_circuit_wire_index(const zk_circuit* c, uint32_t wire, size_t* index);
+/* The circuit's rows through zk_qap_upload_sparse: gate k at w^k, n padded to the next power of two by empty gates (t = x^n - 1).  For
+ * parsed and built circuits alike; the reference's builder leaves the points to the caller, and this is the faster prover here. */
+int zk_circuit_qap_sparse_unity(zk_ctx* ctx, const zk_circuit* c, zk_qap** out);
+
+/* Bit-sliced witness generation for boolean circuits (csrc/boolgen.hip): one 64-bit word holds a wire's value for 64 instances. */
+typedef struct zk_boolgen zk_boolgen;
+/* uploads the circuit's boolean tape; the circuit may be freed afterwards, the context must outlive the generator.  A circuit that is
+ * not boolean (zk_circuit_is_boolean) -> ZK_ERR_UNSUPPORTED with text: such circuits go through zk_witgen_*. */
+int zk_boolgen_create(zk_ctx* ctx, const zk_circuit* c, zk_boolgen** out);
+void zk_boolgen_free(zk_boolgen* g);     /* NULL is a no-op */
+/* The witnesses of `count` input sets.  d_in_bits: packed, instance-major: input i of instance j is bit i % 8 of the byte i / 8 at
+ * d_in_bits + j * in_stride_bytes (a Keccak message is simply its bytes); bits past n_in in the last byte are ignored.
+ * d_weights_out: exactly zk_witgen_run's, count x m x 4 words, canonical, instance-major, so d_weights_out + j*m*4 words is a valid
+ * d_weights[j] of zk_prove_batch_submit / d_weights of zk_prove_dev / zk_qap_check_dev.  Both device pointers.  Complete on return.
+ * count == 0: ZK_OK, nothing touched.  m not the circuit's or in_stride_bytes < ceil(n_in / 8): ZK_ERR_ARG.  Scratch: (m + 1) x 8
+ * bytes per 64 instances in flight, at most the option "boolgen_scratch_kib" (read by zk_boolgen_create; default 4194304 = 4 GiB) --
+ * `count` is not limited by memory (the instances run in chunks and the results do not depend on the chunking), a circuit of which
+ * 64 instances do not fit gives ZK_ERR_SIZE.  Option "boolgen_group_words" (read by zk_boolgen_create): how many 64-instance words one
+ * workgroup of the evaluation owns, 1, 2, 4 or 8; 0 = the default rule.  Option "boolgen_expand_form" (read by zk_boolgen_create): how
+ * the witnesses are written out, 0 = a lane per wire, 1 = a lane pair per wire; the same bytes (DESIGN 4o has the measurement). */
+int zk_boolgen_run(zk_boolgen* g, const void* d_in_bits, size_t in_stride_bytes, size_t count, void* d_weights_out, size_t m);
+/* The same evaluation, returning only the named witness indices, packed as the inputs are: wire wires[i] of instance j is bit i % 8
+ * of the byte i / 8 at d_out_bits + j * out_stride_bytes (unused bits of the last byte are 0, bytes behind it untouched).  This is how
+ * a caller gets a digest -- the public inputs -- without 32 bytes per wire.  wires is a host array of witness indices < m.
+ * Errors as zk_boolgen_run; out_stride_bytes < ceil(n_wires / 8) or an index >= m: ZK_ERR_ARG. */
+int zk_boolgen_eval(zk_boolgen* g, const void* d_in_bits, size_t in_stride_bytes, size_t count, const uint32_t* wires, size_t n_wires,
+                    void* d_out_bits, size_t out_stride_bytes);
 
 /* ------------------------------------------------------------------------------------------
  * CRS  (SigmaG1 / SigmaG2, groth16/mod.rs:105-121)

@@ -16,6 +16,8 @@
 //   groth16::verify((s1, s2), &inputs, proof)   (mod.rs:299-320)   zksnark::groth16::verify(ctx, sigma, inputs, proof)
 //   (none: prove drops the remainder, mod.rs:277)                  zksnark::groth16::is_satisfied / which_is_unsatisfied(ctx, qap, weights)
 //   (none: a CRS is taken on trust)                                zksnark::groth16::check_setup(ctx, qap, sigma)
+//   Circuit<T>, WireId, Word8, Word64, new_and .. keccak256,       zksnark::builder::Circuit (WireId, Word8, Word64), whose finish()
+//   validate_order                 (circuit/builder/mod.rs)        is a zksnark::Circuit; zksnark::Boolgen: bit-sliced witnesses
 //
 // Where the reference panics (division by zero fr.rs:54,69; "Dividend must be non-zero" field/mod.rs:440;
 // unwrap() of a ParseErr) this API throws zksnark::Error carrying the ABI status and message.  The
@@ -114,6 +116,14 @@ class Circuit {
     Circuit(const Circuit&) = delete;
     ~Circuit() { if (c_) zk_circuit_free(c_); }
     const zk_circuit* get() const { return c_; }
+    static Circuit adopt(zk_circuit* c) { return Circuit(c); }   // takes ownership (builder::Circuit::finish)
+    bool is_boolean() const { return zk_circuit_is_boolean(c_) != 0; }
+    // witness index of a builder wire (built circuits; the constant-zero wire has none)
+    size_t wire_index(uint32_t wire) const {
+        size_t i = 0;
+        if (zk_circuit_wire_index(c_, wire, &i) != ZK_OK) throw Error(ZK_ERR_ARG, "wire_index: the wire has no witness index in this circuit");
+        return i;
+    }
     size_t wires() const { return dims()[0]; }
     size_t gates() const { return dims()[1]; }
     size_t input() const { return dims()[2]; }
@@ -122,6 +132,13 @@ class Circuit {
     std::vector<FrLocal> weights(const std::vector<FrLocal>& assignments_in) const {
         std::vector<FrLocal> out(wires());
         int rc = zk_circuit_weights(c_, assignments_in.empty() ? nullptr : assignments_in[0].w.data(), assignments_in.size(), out[0].w.data(), out.size());
+        if (rc != ZK_OK) throw Error(rc, std::string("weights: ") + zk_circuit_last_error(c_));
+        return out;
+    }
+    // the same through the compiled tape (zk_circuit_weights_tape)
+    std::vector<FrLocal> weights_tape(const std::vector<FrLocal>& assignments_in) const {
+        std::vector<FrLocal> out(wires());
+        int rc = zk_circuit_weights_tape(c_, assignments_in.empty() ? nullptr : assignments_in[0].w.data(), assignments_in.size(), out[0].w.data(), out.size());
         if (rc != ZK_OK) throw Error(rc, std::string("weights: ") + zk_circuit_last_error(c_));
         return out;
     }
@@ -165,6 +182,12 @@ class QAP {
     static QAP from_sparse(const Context& c, const Circuit& circuit) {
         zk_qap* q = nullptr;
         c.check(zk_circuit_qap_sparse(c.get(), circuit.get(), &q), "QAP::from_sparse");
+        return QAP(q);
+    }
+    // the same rows at the roots of unity (zk_circuit_qap_sparse_unity): gate k at w^k, n padded to a power of two; the faster prover
+    static QAP from_sparse_unity(const Context& c, const Circuit& circuit) {
+        zk_qap* q = nullptr;
+        c.check(zk_circuit_qap_sparse_unity(c.get(), circuit.get(), &q), "QAP::from_sparse_unity");
         return QAP(q);
     }
     // the struct literal QAP { u, v, w, t, input, degree }: u, v, w = m polynomials of `degree` coefficients
@@ -230,6 +253,154 @@ class QAP {
    private:
     explicit QAP(zk_qap* q) : q_(q) {}
     zk_qap* q_;
+};
+
+// ---- the gate-level circuit builder (circuit/builder/mod.rs, types.rs) -------------------------------
+namespace builder {
+
+typedef uint32_t WireId;                       // WireId(0) = the constant 0, WireId(1) = the constant 1 (mod.rs:91-114)
+typedef std::array<WireId, 8> Word8;           // least significant bit first (types.rs)
+typedef std::array<WireId, 64> Word64;         // 8 Word8s, little endian: bit i of the number is wire i
+enum class Gate { BitChecker = ZK_GATE_BIT_CHECK, Not = ZK_GATE_NOT, And = ZK_GATE_AND, Or = ZK_GATE_OR, Xor = ZK_GATE_XOR, Nand = ZK_GATE_NAND,
+                  Nor = ZK_GATE_NOR, Xnor = ZK_GATE_XNOR, LessThan = ZK_GATE_LESS, GreaterThan = ZK_GATE_GREATER };
+struct ValidateOrder {                         // mod.rs:30-36
+    WireId is_x_within_range, is_y_greater_than_c;
+    std::array<Word8, 32> hash_x_y;
+};
+
+// Circuit<FrLocal> (mod.rs:56-64): the reference's method names over zk_builder_*.  Where the reference takes a gate constructor
+// (Circuit::new_xor) this takes the Gate.  What differs from the reference is listed in zkgpu.h at zk_builder_create.
+class Circuit {
+   public:
+    Circuit() { if (zk_builder_create(&b_) != ZK_OK) throw Error(ZK_ERR_ARG, "zk_builder_create"); }
+    Circuit(Circuit&& o) noexcept : b_(std::exchange(o.b_, nullptr)) {}
+    Circuit(const Circuit&) = delete;
+    ~Circuit() { zk_builder_free(b_); }
+    zk_builder* get() const { return b_; }
+    WireId zero_wire() const { return ZK_WIRE_ZERO; }
+    WireId unity_wire() const { return ZK_WIRE_ONE; }
+    size_t wires() const { size_t w = 0, g = 0; check(zk_builder_dims(b_, &w, &g)); return w; }
+    size_t gates() const { size_t w = 0, g = 0; check(zk_builder_dims(b_, &w, &g)); return g; }
+
+    WireId new_wire() { WireId w; check(zk_builder_new_wires(b_, ZK_WIRE_FIELD, 1, &w)); return w; }   // any field element: not boolean
+    WireId new_bit() { WireId w; check(zk_builder_new_wires(b_, ZK_WIRE_BIT, 1, &w)); return w; }
+    Word8 new_word8() { Word8 w; check(zk_builder_new_wires(b_, ZK_WIRE_BIT, 8, w.data())); return w; }
+    Word64 new_word64() { Word64 w; check(zk_builder_new_wires(b_, ZK_WIRE_BIT, 64, w.data())); return w; }
+    std::vector<Word8> new_word8_vec(size_t size) { std::vector<Word8> v(size); for (auto& w : v) w = new_word8(); return v; }
+    Word8 const_word8(uint8_t x) const { Word8 w; for (int i = 0; i < 8; ++i) w[i] = (x >> i) & 1; return w; }
+    Word64 const_word64(uint64_t x) const { Word64 w; for (int i = 0; i < 64; ++i) w[i] = (WireId)((x >> i) & 1); return w; }
+
+    typedef std::vector<std::pair<FrLocal, WireId>> Side;
+    WireId new_sub_circuit(const Side& lhs, const Side& rhs) {
+        std::vector<uint64_t> lw, rw;
+        std::vector<WireId> li, ri;
+        for (const auto& t : lhs) { lw.insert(lw.end(), t.first.w.begin(), t.first.w.end()); li.push_back(t.second); }
+        for (const auto& t : rhs) { rw.insert(rw.end(), t.first.w.begin(), t.first.w.end()); ri.push_back(t.second); }
+        WireId out;
+        check(zk_builder_sub_circuit(b_, lw.data(), li.data(), li.size(), rw.data(), ri.data(), ri.size(), &out));
+        return out;
+    }
+    WireId gate(Gate g, WireId x, WireId y = ZK_WIRE_ZERO) { WireId o; check(zk_builder_gate(b_, (int)g, x, y, &o)); return o; }
+    WireId new_bit_checker(WireId x) { return gate(Gate::BitChecker, x); }
+    WireId new_not(WireId x) { return gate(Gate::Not, x); }
+    WireId new_and(WireId x, WireId y) { return gate(Gate::And, x, y); }
+    WireId new_or(WireId x, WireId y) { return gate(Gate::Or, x, y); }
+    WireId new_xor(WireId x, WireId y) { return gate(Gate::Xor, x, y); }
+    WireId new_nand(WireId x, WireId y) { return gate(Gate::Nand, x, y); }
+    WireId new_nor(WireId x, WireId y) { return gate(Gate::Nor, x, y); }
+    WireId new_xnor(WireId x, WireId y) { return gate(Gate::Xnor, x, y); }
+    // w (w - 1) = 0 without output wire: what forces an input to be 0 or 1 (not in the reference)
+    void assert_bit(WireId w) { check(zk_builder_assert_bit(b_, w)); }
+
+    template <class Wires>
+    WireId fan_in(const Wires& inputs, Gate g) { WireId o; check(zk_builder_fan_in(b_, (int)g, inputs.data(), inputs.size(), &o)); return o; }
+    template <class Wires>
+    Wires bitwise_op(const Wires& l, const Wires& r, Gate g) {
+        if (l.size() != r.size()) throw Error(ZK_ERR_ARG, "bitwise_op: arrays of different lengths");
+        Wires o = l;
+        check(zk_builder_bitwise(b_, (int)g, l.data(), r.data(), l.size(), o.data()));
+        return o;
+    }
+    Word8 u8_bitwise_op(const Word8& l, const Word8& r, Gate g) { return bitwise_op(l, r, g); }
+    Word64 u64_bitwise_op(const Word64& l, const Word64& r, Gate g) { return bitwise_op(l, r, g); }
+    template <class Wires>
+    Wires unary_op(const Wires& x, Gate g) { Wires o = x; check(zk_builder_bitwise(b_, (int)g, x.data(), nullptr, x.size(), o.data())); return o; }
+    Word8 u8_unary_op(const Word8& x, Gate g) { return unary_op(x, g); }
+    Word64 u64_unary_op(const Word64& x, Gate g) { return unary_op(x, g); }
+
+    template <class Wires> WireId is_equal(const Wires& l, const Wires& r) { return compare(ZK_CMP_EQUAL, l, &r); }
+    template <class Wires> WireId is_equal_zero(const Wires& x) { return compare(ZK_CMP_EQUAL_ZERO, x, (const Wires*)nullptr); }
+    template <class Wires> WireId less_than(const Wires& l, const Wires& r) { return compare(ZK_CMP_LESS, l, &r); }
+    template <class Wires> WireId less_than_eq(const Wires& l, const Wires& r) { return compare(ZK_CMP_LESS_EQ, l, &r); }
+    template <class Wires> WireId greater_than(const Wires& l, const Wires& r) { return compare(ZK_CMP_GREATER, l, &r); }
+    template <class Wires> WireId greater_than_eq(const Wires& l, const Wires& r) { return compare(ZK_CMP_GREATER_EQ, l, &r); }
+
+    // the sponge in general form: rate in bytes, the delimiter byte, rounds of Keccak-f[1600] (24 = the real permutation)
+    std::vector<Word8> keccak(const std::vector<Word8>& input, unsigned rate, unsigned delim, unsigned rounds, size_t out_bytes) {
+        std::vector<Word8> out(out_bytes);
+        check(zk_builder_keccak(b_, input.empty() ? nullptr : input[0].data(), input.size(), rate, delim, rounds, out.empty() ? nullptr : out[0].data(),
+                                out_bytes));
+        return out;
+    }
+    std::array<Word8, 32> keccak256(const std::vector<Word8>& input) {
+        std::array<Word8, 32> out;
+        check(zk_builder_keccak(b_, input.empty() ? nullptr : input[0].data(), input.size(), 136, 0x01, 24, out[0].data(), 32));
+        return out;
+    }
+    // the reference absorbs a stream byte by byte; the sub-circuits and their order are keccak256's
+    std::array<Word8, 32> keccak256_stream(const std::vector<Word8>& input) { return keccak256(input); }
+    ValidateOrder validate_order(const Word64& input_x, const std::pair<Word64, Word64>& pub_range, const Word64& input_y, const Word64& pub_c) {
+        const WireId x_geq = greater_than_eq(input_x, pub_range.first);
+        const WireId x_leq = less_than_eq(input_x, pub_range.second);
+        ValidateOrder v;
+        v.is_x_within_range = new_and(x_geq, x_leq);
+        v.is_y_greater_than_c = greater_than_eq(input_y, pub_c);
+        std::vector<Word8> stream(16);
+        for (int k = 0; k < 8; ++k)
+            for (int i = 0; i < 8; ++i) { stream[k][i] = input_x[8 * k + i]; stream[8 + k][i] = input_y[8 * k + i]; }
+        v.hash_x_y = keccak256_stream(stream);
+        return v;
+    }
+    // -> the circuit as a RootRepresentation: witness = [1], `verify` as given, the other inputs in creation order, the other wires by id
+    zksnark::Circuit finish(const std::vector<WireId>& verify) {
+        zk_circuit* c = nullptr;
+        check(zk_builder_finish(b_, verify.data(), verify.size(), &c));
+        return zksnark::Circuit::adopt(c);
+    }
+
+   private:
+    void check(int rc) const {
+        if (rc != ZK_OK) throw Error(rc, std::string("builder: ") + zk_builder_last_error(b_));
+    }
+    template <class Wires>
+    WireId compare(int kind, const Wires& l, const Wires* r) {
+        if (r && r->size() != l.size()) throw Error(ZK_ERR_ARG, "comparator: arrays of different lengths");
+        WireId o;
+        check(zk_builder_compare(b_, kind, l.data(), r ? r->data() : nullptr, l.size(), &o));
+        return o;
+    }
+    zk_builder* b_ = nullptr;
+};
+
+}  // namespace builder
+
+// zk_boolgen_*: the witnesses of a boolean built circuit for many input sets at once, bit-sliced (device pointers in and out)
+class Boolgen {
+   public:
+    Boolgen(const Context& c, const Circuit& circuit) : c_(c) { c.check(zk_boolgen_create(c.get(), circuit.get(), &g_), "Boolgen"); }
+    Boolgen(const Boolgen&) = delete;
+    ~Boolgen() { zk_boolgen_free(g_); }
+    void run(const void* d_in_bits, size_t in_stride_bytes, size_t count, void* d_weights_out, size_t m) const {
+        c_.check(zk_boolgen_run(g_, d_in_bits, in_stride_bytes, count, d_weights_out, m), "Boolgen::run");
+    }
+    void eval(const void* d_in_bits, size_t in_stride_bytes, size_t count, const std::vector<uint32_t>& wires, void* d_out_bits,
+              size_t out_stride_bytes) const {
+        c_.check(zk_boolgen_eval(g_, d_in_bits, in_stride_bytes, count, wires.data(), wires.size(), d_out_bits, out_stride_bytes), "Boolgen::eval");
+    }
+
+   private:
+    const Context& c_;
+    zk_boolgen* g_ = nullptr;
 };
 
 namespace groth16 {

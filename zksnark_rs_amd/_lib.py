@@ -164,6 +164,26 @@ SIGNATURES = {
     "zk_witgen_create": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
     "zk_witgen_free": (None, [C.c_void_p]),
     "zk_witgen_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t]),
+    "zk_builder_create": (C.c_int, [C.POINTER(C.c_void_p)]),
+    "zk_builder_free": (None, [C.c_void_p]),
+    "zk_builder_last_error": (C.c_char_p, [C.c_void_p]),
+    "zk_builder_dims": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "zk_builder_new_wires": (C.c_int, [C.c_void_p, C.c_int, C.c_size_t, u32p]),
+    "zk_builder_sub_circuit": (C.c_int, [C.c_void_p, u64p, u32p, C.c_size_t, u64p, u32p, C.c_size_t, u32p]),
+    "zk_builder_gate": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, u32p]),
+    "zk_builder_bitwise": (C.c_int, [C.c_void_p, C.c_int, u32p, u32p, C.c_size_t, u32p]),
+    "zk_builder_fan_in": (C.c_int, [C.c_void_p, C.c_int, u32p, C.c_size_t, u32p]),
+    "zk_builder_compare": (C.c_int, [C.c_void_p, C.c_int, u32p, u32p, C.c_size_t, u32p]),
+    "zk_builder_keccak": (C.c_int, [C.c_void_p, u32p, C.c_size_t, C.c_uint, C.c_uint, C.c_uint, u32p, C.c_size_t]),
+    "zk_builder_assert_bit": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "zk_builder_finish": (C.c_int, [C.c_void_p, u32p, C.c_size_t, C.POINTER(C.c_void_p)]),
+    "zk_circuit_is_boolean": (C.c_int, [C.c_void_p]),
+    "zk_circuit_wire_index": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_size_t)]),
+    "zk_circuit_qap_sparse_unity": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "zk_boolgen_create": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "zk_boolgen_free": (None, [C.c_void_p]),
+    "zk_boolgen_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t]),
+    "zk_boolgen_eval": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, u32p, C.c_size_t, C.c_void_p, C.c_size_t]),
     "zk_msm_auto_window": (C.c_int, [C.c_size_t]),
     "zk_msm_auto_window_g2": (C.c_int, [C.c_size_t]),
     "zk_circuit_qap": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),

@@ -1,0 +1,288 @@
+// boolgen.hip -- zk_boolgen_*: the witnesses of a BOOLEAN built circuit (builder.hpp) for many input sets at once, bit-sliced.
+//
+// Where k_witgen (witgen.hip) keeps a 32-byte Montgomery slot per wire and instance and pays a 254-bit multiplication per AND, every
+// value here is 0 or 1, so a wire is one uint64 per 64 instances and a gate one 64-bit logic operation for all 64 of them.
+//   state      uint64 per (witness index, instance word), index-major: state[s * nw + w]; bit l of word w is instance 64 w + l.
+//              Index 0 is the constant 1 (all ones), index m the constant 0.
+//   load       a transposition (k_bool_load): lane = instance, one wave64 __ballot per input bit is that input's word.  Instances
+//              behind `count` in the last word load 0 and are never written out.
+//   evaluate   the circuit's boolean tape (one op per sub-circuit, sorted by level), level by level (k_bool_eval): a workgroup owns G
+//              consecutive instance words, the (op, word) pairs of a level are strided over its lanes with the word index fastest,
+//              so neighbouring lanes touch neighbouring words of one slot; __syncthreads() between levels.  No lane returns early.
+//   expand     the bandwidth step (k_bool_expand): (instance, wire) -> 32 bytes, word 0 = the bit, words 1..3 = 0, instance-major:
+//              exactly what zk_witgen_run writes.  Lane = wire: it loads its slot's word once and walks the 64 instances; a wave's
+//              stores cover 2 KiB contiguous of one instance's witness.
+//   pack       zk_boolgen_eval instead of expand (k_bool_pack): the named wires only, packed the way the inputs are.
+// Words run in chunks of as many as the scratch cap holds (option "boolgen_scratch_kib"); every word is independent of the others, so
+// the result does not depend on the chunking.  Mixed boolean / field circuits stay on the tape (zk_witgen_*).
+#include "pipeline.hpp"
+#include "circuit.hpp"
+
+struct zk_boolgen {
+    zk_ctx* ctx = nullptr;
+    size_t n_in = 0, m = 0, levels = 0;
+    size_t scratch_cap = 0;                 // bytes
+    unsigned group_words = 0;               // 0 = by rule
+    bool expand_pair = false;
+    zk::DevBuf<zk::BoolOp> ops;
+    zk::DevBuf<uint32_t> level_ptr, in_wit, sel;
+    zk::DevBuf<uint64_t> state;
+};
+
+namespace zk {
+
+static constexpr unsigned BG_EVAL_THREADS = 1024;
+static constexpr unsigned BG_LOAD_WAVES = 4;
+static constexpr unsigned BG_EXPAND_THREADS = 256;
+static constexpr size_t BG_MAX_CHUNK_WORDS = 32768;   // a grid dimension of the expansion
+
+// G rule: the largest of 8, 4, 2 words per workgroup that still leaves one workgroup per compute unit, else 1.  More words per
+// workgroup read the tape fewer times and make a slot's access G * 8 contiguous bytes; fewer keep every compute unit busy.
+static unsigned boolgen_group_words(size_t words, int cu_count) {
+    for (unsigned g = 8; g > 1; g /= 2)
+        if (words / g >= (size_t)cu_count) return g;
+    return 1;
+}
+
+// grid: one workgroup per instance word of the chunk; word0 = first word of the chunk (global numbering)
+__global__ void __launch_bounds__(64 * BG_LOAD_WAVES)
+k_bool_load(const uint8_t* __restrict__ in, size_t stride, size_t count, size_t word0, const uint32_t* __restrict__ in_wit, unsigned n_in, unsigned m,
+            size_t nw, uint64_t* __restrict__ state) {
+    const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const size_t w = blockIdx.x;
+    const size_t j = (word0 + w) * 64 + lane;
+    const bool live = j < count;
+    if (threadIdx.x == 0) {
+        state[w] = ~0ull;                     // index 0: the constant 1
+        state[(size_t)m * nw + w] = 0;        // index m: the constant 0
+    }
+    const unsigned n_bytes = (n_in + 7) / 8;
+    for (unsigned k = wave; k < n_bytes; k += BG_LOAD_WAVES) {        // wave-uniform trip count: every lane takes part in every ballot
+        const unsigned byte = live ? in[j * stride + k] : 0u;
+        const unsigned bits = min(8u, n_in - 8 * k);
+        for (unsigned b = 0; b < bits; ++b) {
+            const unsigned long long word = __ballot((byte >> b) & 1u);
+            if (lane == 0) state[(size_t)in_wit[8 * k + b] * nw + w] = word;
+        }
+    }
+}
+
+__device__ __forceinline__ uint64_t bool_apply(uint32_t kind, uint64_t a, uint64_t b) {
+    switch (kind) {
+        case BOOL_NOT: return ~a;
+        case BOOL_AND: return a & b;
+        case BOOL_OR: return a | b;
+        case BOOL_XOR: return a ^ b;
+        case BOOL_NOR: return ~(a | b);
+        case BOOL_XNOR: return ~(a ^ b);
+        case BOOL_LESS: return ~a & b;
+        case BOOL_GREATER: return a & ~b;
+        default: return 0;                    // BOOL_ZERO
+    }
+}
+
+// grid: one workgroup per G = 1 << g_log words of the chunk
+__global__ void __launch_bounds__(BG_EVAL_THREADS)
+k_bool_eval(const BoolOp* __restrict__ ops, const uint32_t* __restrict__ level_ptr, unsigned levels, unsigned g_log, size_t nw, uint64_t* state) {
+    const size_t w_base = (size_t)blockIdx.x << g_log;
+    const unsigned g_mask = (1u << g_log) - 1;
+    for (unsigned l = 0; l < levels; ++l) {
+        const unsigned begin = level_ptr[l], end = level_ptr[l + 1];
+        const size_t pairs = (size_t)(end - begin) << g_log;
+        for (size_t idx = threadIdx.x; idx < pairs; idx += BG_EVAL_THREADS) {
+            const size_t w = w_base + (idx & g_mask);
+            if (w < nw) {
+                const uint4 raw = reinterpret_cast<const uint4*>(ops)[begin + (idx >> g_log)];   // {dst, a, b, kind}
+                const uint64_t a = state[(size_t)raw.y * nw + w], b = state[(size_t)raw.z * nw + w];
+                state[(size_t)raw.x * nw + w] = bool_apply(raw.w, a, b);
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// grid: (ceil(m / threads), words of the chunk)
+__global__ void __launch_bounds__(BG_EXPAND_THREADS)
+k_bool_expand(const uint64_t* __restrict__ state, size_t nw, size_t word0, size_t count, unsigned m, uint64_t* __restrict__ out) {
+    const unsigned s = blockIdx.x * BG_EXPAND_THREADS + threadIdx.x;
+    const size_t w = blockIdx.y;
+    const bool mine = s < m;
+    const uint64_t word = mine ? state[(size_t)s * nw + w] : 0;
+    const size_t j0 = (word0 + w) * 64;
+    const unsigned n = (unsigned)min((size_t)64, count - j0);          // j0 < count for every word of a chunk
+    if (!mine) return;                                                  // (no barrier and no cross-lane operation follows)
+    uint4* o = reinterpret_cast<uint4*>(out + (j0 * m + s) * 4);
+    for (unsigned l = 0; l < n; ++l) {
+        o[0] = make_uint4((unsigned)((word >> l) & 1), 0, 0, 0);
+        o[1] = make_uint4(0, 0, 0, 0);
+        o += (size_t)m * 2;
+    }
+}
+
+// The same bytes with a lane PAIR per wire: the even lane stores {bit, 0}, the odd lane the two zero words, so one wave instruction
+// covers 1 KiB contiguous.  grid: (ceil(2 m / threads), words of the chunk)
+__global__ void __launch_bounds__(BG_EXPAND_THREADS)
+k_bool_expand_pair(const uint64_t* __restrict__ state, size_t nw, size_t word0, size_t count, unsigned m, uint64_t* __restrict__ out) {
+    const unsigned t = blockIdx.x * BG_EXPAND_THREADS + threadIdx.x;
+    const unsigned s = t >> 1;
+    const size_t w = blockIdx.y;
+    if (s >= m) return;                                                 // (no barrier and no cross-lane operation follows)
+    const uint64_t word = (t & 1) ? 0 : state[(size_t)s * nw + w];      // the odd lane writes zeros whatever the bit
+    const size_t j0 = (word0 + w) * 64;
+    const unsigned n = (unsigned)min((size_t)64, count - j0);
+    uint4* o = reinterpret_cast<uint4*>(out + j0 * m * 4) + t;
+    for (unsigned l = 0; l < n; ++l) {
+        *o = make_uint4((unsigned)((word >> l) & 1), 0, 0, 0);
+        o += (size_t)m * 2;
+    }
+}
+
+// grid: one workgroup per word of the chunk; lane = instance
+__global__ void __launch_bounds__(64 * BG_LOAD_WAVES)
+k_bool_pack(const uint64_t* __restrict__ state, size_t nw, size_t word0, size_t count, const uint32_t* __restrict__ sel, unsigned n_sel,
+            uint8_t* __restrict__ out, size_t stride) {
+    const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const size_t w = blockIdx.x;
+    const size_t j = (word0 + w) * 64 + lane;
+    const bool live = j < count;
+    const unsigned n_bytes = (n_sel + 7) / 8;
+    for (unsigned k = wave; k < n_bytes; k += BG_LOAD_WAVES) {
+        const unsigned bits = min(8u, n_sel - 8 * k);
+        unsigned v = 0;
+        for (unsigned b = 0; b < bits; ++b) v |= (unsigned)((state[(size_t)sel[8 * k + b] * nw + w] >> lane) & 1) << b;
+        if (live) out[j * stride + k] = (uint8_t)v;
+    }
+}
+
+static zk_boolgen* boolgen_create(zk_ctx* ctx, const zk_circuit& c) {
+    ZK_REQUIRE(c.built && c.built->boolean, ZK_ERR_UNSUPPORTED,
+               "boolgen: the circuit is not boolean (a parsed program, a field input or a general sub-circuit); use zk_witgen_create");
+    const Built& p = *c.built;
+    const size_t m = c.u.size();
+    ZK_REQUIRE(m < (1u << 31) && p.bool_ops.size() < (1u << 31), ZK_ERR_SIZE, "boolgen: circuit too large");
+    const long gw = ctx->opt_boolgen_group_words;
+    ZK_REQUIRE(gw == 0 || gw == 1 || gw == 2 || gw == 4 || gw == 8, ZK_ERR_ARG, "boolgen: option boolgen_group_words must be 0, 1, 2, 4 or 8");
+    std::unique_ptr<zk_boolgen> g(new zk_boolgen());
+    g->ctx = ctx;
+    g->n_in = p.in_wit.size(); g->m = m;
+    g->levels = p.bool_level_ptr.empty() ? 0 : p.bool_level_ptr.size() - 1;
+    g->scratch_cap = (size_t)std::max<long>(ctx->opt_boolgen_scratch_kib, 0) * 1024;
+    g->group_words = (unsigned)gw;
+    g->expand_pair = ctx->opt_boolgen_expand_form != 0;
+    hipStream_t st = ctx->stream;
+    auto up = [&](auto& buf, const auto& host) {
+        buf.alloc(std::max<size_t>(host.size(), 1));   // never a null array
+        if (!host.empty()) ZK_HIP(hipMemcpyAsync(buf.p, host.data(), host.size() * sizeof(host[0]), hipMemcpyHostToDevice, st));
+    };
+    up(g->ops, p.bool_ops);
+    up(g->in_wit, p.in_wit);
+    const std::vector<uint32_t> lp = p.bool_level_ptr.empty() ? std::vector<uint32_t>{0} : p.bool_level_ptr;
+    up(g->level_ptr, lp);
+    ZK_HIP(hipStreamSynchronize(st));   // the host vectors may go away with the circuit
+    return g.release();
+}
+
+// load + evaluate per chunk, then `emit(word0, words, nw)` on the chunk's state
+template <class Emit>
+static void boolgen_chunks(zk_boolgen& g, const void* d_in, size_t stride, size_t count, Emit&& emit) {
+    zk_ctx* ctx = g.ctx;
+    hipStream_t st = ctx->stream;
+    const size_t word_bytes = (g.m + 1) * sizeof(uint64_t);
+    const size_t words = (count + 63) / 64;
+    const size_t fit = g.scratch_cap / word_bytes;
+    ZK_REQUIRE(fit >= 1, ZK_ERR_SIZE, "boolgen: one word of 64 instances needs " + std::to_string((word_bytes + 1023) >> 10) +
+                                          " KiB of scratch, more than the option boolgen_scratch_kib allows");
+    const size_t chunk = std::min(std::min(words, fit), BG_MAX_CHUNK_WORDS);
+    g.state.ensure(chunk * (g.m + 1));
+    for (size_t w0 = 0; w0 < words; w0 += chunk) {       // same stream: a chunk starts when the one before has left the state
+        const size_t nw = std::min(chunk, words - w0);
+        const unsigned G = g.group_words ? g.group_words : boolgen_group_words(nw, ctx->cu_count);
+        unsigned g_log = 0;
+        while ((1u << g_log) < G) ++g_log;
+        {
+            ProfScope ps(ctx, "boolgen_load", 0.0);
+            hipLaunchKernelGGL(k_bool_load, dim3((unsigned)nw), dim3(64 * BG_LOAD_WAVES), 0, st, (const uint8_t*)d_in, stride, count, w0, g.in_wit.p,
+                               (unsigned)g.n_in, (unsigned)g.m, nw, g.state.p);
+        }
+        if (g.levels) {
+            ProfScope ps(ctx, "boolgen_eval", 0.0);
+            hipLaunchKernelGGL(k_bool_eval, dim3((unsigned)((nw + G - 1) / G)), dim3(BG_EVAL_THREADS), 0, st, g.ops.p, g.level_ptr.p, (unsigned)g.levels,
+                               g_log, nw, g.state.p);
+        }
+        ZK_HIP(hipGetLastError());
+        emit(w0, nw);
+        ZK_HIP(hipGetLastError());
+    }
+    ZK_HIP(hipStreamSynchronize(st));
+    ctx->resolve_profile();
+}
+
+static void boolgen_run(zk_boolgen& g, const void* d_in, size_t stride, size_t count, void* d_out) {
+    zk_ctx* ctx = g.ctx;
+    boolgen_chunks(g, d_in, stride, count, [&](size_t w0, size_t nw) {
+        const size_t inst = std::min(count - w0 * 64, nw * 64);
+        ProfScope ps(ctx, "boolgen_expand", (double)inst * g.m * 32.0);
+        if (g.expand_pair)
+            hipLaunchKernelGGL(k_bool_expand_pair, dim3(ceil_div(2 * g.m, BG_EXPAND_THREADS), (unsigned)nw), dim3(BG_EXPAND_THREADS), 0, ctx->stream,
+                               g.state.p, nw, w0, count, (unsigned)g.m, (uint64_t*)d_out);
+        else
+            hipLaunchKernelGGL(k_bool_expand, dim3(ceil_div(g.m, BG_EXPAND_THREADS), (unsigned)nw), dim3(BG_EXPAND_THREADS), 0, ctx->stream, g.state.p, nw,
+                               w0, count, (unsigned)g.m, (uint64_t*)d_out);
+    });
+}
+
+static void boolgen_eval(zk_boolgen& g, const void* d_in, size_t stride, size_t count, const uint32_t* wires, size_t n_wires, void* d_out,
+                         size_t out_stride) {
+    zk_ctx* ctx = g.ctx;
+    g.sel.ensure(std::max<size_t>(n_wires, 1));
+    if (n_wires) ZK_HIP(hipMemcpyAsync(g.sel.p, wires, n_wires * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    boolgen_chunks(g, d_in, stride, count, [&](size_t w0, size_t nw) {
+        ProfScope ps(ctx, "boolgen_pack", 0.0);
+        hipLaunchKernelGGL(k_bool_pack, dim3((unsigned)nw), dim3(64 * BG_LOAD_WAVES), 0, ctx->stream, g.state.p, nw, w0, count, g.sel.p, (unsigned)n_wires,
+                           (uint8_t*)d_out, out_stride);
+    });
+}
+
+}  // namespace zk
+
+using namespace zk;
+
+extern "C" {
+
+int zk_boolgen_create(zk_ctx* ctx, const zk_circuit* c, zk_boolgen** out) {
+    if (!ctx || !c || !out) return ZK_ERR_ARG;
+    *out = nullptr;
+    return guarded(ctx, [&] { *out = boolgen_create(ctx, *c); });
+}
+void zk_boolgen_free(zk_boolgen* g) {
+    if (!g) return;
+    (void)hipSetDevice(g->ctx->device);
+    delete g;
+}
+int zk_boolgen_run(zk_boolgen* g, const void* d_in_bits, size_t in_stride_bytes, size_t count, void* d_weights_out, size_t m) {
+    if (!g) return ZK_ERR_ARG;
+    return guarded(g->ctx, [&] {
+        ZK_REQUIRE(m == g->m, ZK_ERR_ARG, "StructureErr(None, weights buffer size mismatch)");
+        ZK_REQUIRE(in_stride_bytes >= (g->n_in + 7) / 8, ZK_ERR_ARG, "boolgen: in_stride_bytes is shorter than the packed inputs of one instance");
+        if (count == 0) return;
+        ZK_REQUIRE(d_weights_out && (d_in_bits || !g->n_in), ZK_ERR_ARG, "boolgen: null device pointer");
+        boolgen_run(*g, d_in_bits, in_stride_bytes, count, d_weights_out);
+    });
+}
+int zk_boolgen_eval(zk_boolgen* g, const void* d_in_bits, size_t in_stride_bytes, size_t count, const uint32_t* wires, size_t n_wires,
+                    void* d_out_bits, size_t out_stride_bytes) {
+    if (!g) return ZK_ERR_ARG;
+    return guarded(g->ctx, [&] {
+        ZK_REQUIRE(in_stride_bytes >= (g->n_in + 7) / 8, ZK_ERR_ARG, "boolgen: in_stride_bytes is shorter than the packed inputs of one instance");
+        ZK_REQUIRE(out_stride_bytes >= (n_wires + 7) / 8, ZK_ERR_ARG, "boolgen: out_stride_bytes is shorter than the packed wires of one instance");
+        ZK_REQUIRE(wires || !n_wires, ZK_ERR_ARG, "boolgen: null wire list");
+        ZK_REQUIRE(n_wires < (1u << 31), ZK_ERR_ARG, "boolgen: too many wires named");
+        for (size_t i = 0; i < n_wires; ++i)
+            ZK_REQUIRE(wires[i] < g->m, ZK_ERR_ARG, "boolgen: witness index " + std::to_string(wires[i]) + " is not below m");
+        if (count == 0 || n_wires == 0) return;
+        ZK_REQUIRE(d_out_bits && (d_in_bits || !g->n_in), ZK_ERR_ARG, "boolgen: null device pointer");
+        boolgen_eval(*g, d_in_bits, in_stride_bytes, count, wires, n_wires, d_out_bits, out_stride_bytes);
+    });
+}
+
+}  // extern "C"

@@ -1,0 +1,115 @@
+// builder.hip -- zk_builder_*: the C ABI over builder.hpp (host code only; no context, no device).
+#include "builder.hpp"
+
+namespace zk {
+
+template <class Fn>
+static int builder_guard(zk_builder* b, Fn&& fn) {
+    if (!b) return ZK_ERR_ARG;
+    try {
+        BuilderOps ops{*b};
+        ops.live();
+        fn(ops);
+        return ZK_OK;
+    } catch (const ParseError& e) { b->last_error = e.msg; return e.status; }
+    catch (const std::exception& e) { b->last_error = e.what(); return ZK_ERR_ARG; }
+    catch (...) { b->last_error = "unknown error"; return ZK_ERR_ARG; }
+}
+
+}  // namespace zk
+
+using namespace zk;
+
+extern "C" {
+
+int zk_builder_create(zk_builder** out) {
+    if (!out) return ZK_ERR_ARG;
+    *out = nullptr;
+    try { *out = new zk_builder(); } catch (...) { return ZK_ERR_ARG; }
+    return ZK_OK;
+}
+void zk_builder_free(zk_builder* b) { delete b; }
+const char* zk_builder_last_error(const zk_builder* b) { return b ? b->last_error.c_str() : "null builder"; }
+int zk_builder_dims(const zk_builder* b, size_t* wires, size_t* gates) {
+    if (!b) return ZK_ERR_ARG;
+    return builder_guard(const_cast<zk_builder*>(b), [&](BuilderOps& o) {
+        if (wires) *wires = o.b.kind.size();
+        if (gates) *gates = o.b.subs.size();
+    });
+}
+int zk_builder_new_wires(zk_builder* b, int kind, size_t count, uint32_t* out) {
+    return builder_guard(b, [&](BuilderOps& o) {
+        if (kind != ZK_WIRE_BIT && kind != ZK_WIRE_FIELD) BuilderOps::fail("unknown wire kind " + std::to_string(kind));
+        if (count && !out) BuilderOps::fail("null output array");
+        for (size_t i = 0; i < count; ++i) out[i] = o.new_wire(kind == ZK_WIRE_BIT ? 1 : 2);
+    });
+}
+int zk_builder_sub_circuit(zk_builder* b, const uint64_t* left_weights, const uint32_t* left_wires, size_t nl, const uint64_t* right_weights,
+                           const uint32_t* right_wires, size_t nr, uint32_t* out) {
+    return builder_guard(b, [&](BuilderOps& o) {
+        if (!out || (nl && (!left_weights || !left_wires)) || (nr && (!right_weights || !right_wires))) BuilderOps::fail("null array");
+        *out = o.general(left_weights, left_wires, nl, right_weights, right_wires, nr);
+    });
+}
+int zk_builder_gate(zk_builder* b, int kind, uint32_t x, uint32_t y, uint32_t* out) {
+    return builder_guard(b, [&](BuilderOps& o) {
+        if (!out) BuilderOps::fail("null output");
+        o.known(x);
+        if (!BuilderOps::unary(kind)) o.known(y);
+        *out = o.gate(kind, x, y);
+    });
+}
+int zk_builder_bitwise(zk_builder* b, int kind, const uint32_t* x, const uint32_t* y, size_t n, uint32_t* out) {
+    return builder_guard(b, [&](BuilderOps& o) {
+        const bool un = BuilderOps::unary(kind);
+        if (kind < ZK_GATE_BIT_CHECK || kind > ZK_GATE_GREATER) BuilderOps::fail("unknown gate kind " + std::to_string(kind));
+        if (n && (!x || !out || (!un && !y))) BuilderOps::fail("null array");
+        for (size_t i = 0; i < n; ++i) { o.known(x[i]); if (!un) o.known(y[i]); }
+        for (size_t i = 0; i < n; ++i) {
+            const uint32_t r = o.gate(kind, x[i], un ? 0 : y[i]);   // out may alias x or y
+            out[i] = r;
+        }
+    });
+}
+int zk_builder_fan_in(zk_builder* b, int kind, const uint32_t* x, size_t n, uint32_t* out) {
+    return builder_guard(b, [&](BuilderOps& o) {
+        if (kind < ZK_GATE_BIT_CHECK || kind > ZK_GATE_GREATER || BuilderOps::unary(kind)) BuilderOps::fail("fan_in takes a two-input gate kind");
+        if (!n || !x || !out) BuilderOps::fail("fan_in: the input must have at least one element");
+        for (size_t i = 0; i < n; ++i) o.known(x[i]);
+        uint32_t acc = x[0];
+        for (size_t i = 1; i < n; ++i) acc = o.gate(kind, acc, x[i]);
+        *out = acc;
+    });
+}
+int zk_builder_compare(zk_builder* b, int kind, const uint32_t* left, const uint32_t* right, size_t n_bits, uint32_t* out) {
+    return builder_guard(b, [&](BuilderOps& o) {
+        if (kind < ZK_CMP_EQUAL || kind > ZK_CMP_GREATER_EQ) BuilderOps::fail("unknown comparator " + std::to_string(kind));
+        const bool one_sided = kind == ZK_CMP_EQUAL_ZERO;
+        if (!n_bits || !left || !out || (!one_sided && !right)) BuilderOps::fail("comparator: the inputs must have at least one wire");
+        for (size_t i = 0; i < n_bits; ++i) { o.known(left[i]); if (!one_sided) o.known(right[i]); }
+        *out = o.compare(kind, left, right, n_bits);
+    });
+}
+int zk_builder_keccak(zk_builder* b, const uint32_t* in_wires, size_t n_bytes, unsigned rate_bytes, unsigned delim, unsigned rounds,
+                      uint32_t* out_wires, size_t out_bytes) {
+    return builder_guard(b, [&](BuilderOps& o) {
+        if ((n_bytes && !in_wires) || (out_bytes && !out_wires)) BuilderOps::fail("null array");
+        o.keccak(in_wires, n_bytes, rate_bytes, delim, rounds, out_wires, out_bytes);
+    });
+}
+int zk_builder_assert_bit(zk_builder* b, uint32_t wire) {
+    return builder_guard(b, [&](BuilderOps& o) {
+        o.known(wire);
+        o.assert_bit(wire);
+    });
+}
+int zk_builder_finish(zk_builder* b, const uint32_t* verify_wires, size_t n_verify, zk_circuit** out) {
+    if (!out) return ZK_ERR_ARG;
+    *out = nullptr;
+    return builder_guard(b, [&](BuilderOps& o) {
+        if (n_verify && !verify_wires) BuilderOps::fail("null array");
+        *out = builder_finish(o.b, verify_wires, n_verify);
+    });
+}
+
+}  // extern "C"

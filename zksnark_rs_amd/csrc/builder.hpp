@@ -1,0 +1,459 @@
+// builder.hpp -- the reference's gate-level circuit builder (host code, as in the reference) and what a finished circuit needs to be an
+// ordinary zk_circuit: rows, the two host evaluators' program, the field tape of witgen.hip and the boolean tape of boolgen.hip.
+//
+//   Circuit::new, zero / unity wire, new_wire        circuit/builder/mod.rs:91-125
+//   new_sub_circuit                                  mod.rs:491-557 (weights and wires of (sum left) * (sum right) = out)
+//   new_bit_checker .. new_xnor, fan_in, bitwise_op  mod.rs:723-827
+//   new_less_than, new_greater_than, new_equality    mod.rs:939-957
+//   is_equal .. greater_than                         mod.rs:995-1241
+//   keccakf_1600, absorb, xorin, pad, squeeze        mod.rs:1247-1398, tables types.rs:295-328
+//
+// Every constructor emits exactly the reference's sub-circuits in the reference's order, so gate counts and weights are its own.
+// What differs, on purpose: wires are numbered and ordered deterministically (the reference iterates a HashMap); entries on the
+// constant-zero wire are dropped instead of becoming a witness wire that no constraint pins; its builder -> DummyRep conversion
+// (num_wires empty rows in front) is not reproduced; zk_builder_assert_bit exists.  Header-only and free of device code, so
+// tests/cpp/builder_host.hip compiles it alone under the sanitizers.
+#pragma once
+#include <array>
+#include <map>
+#include "circuit.hpp"
+
+struct zk_builder {
+    struct Term { zk::Fr w; uint32_t wire; };
+    struct Sub { uint32_t l0, r0, end, out, bkind, a, b; };
+    std::vector<uint8_t> kind{0, 0};   // per wire id: 0 = a constant (ids 0 and 1), 1 = bit input, 2 = field input, 3 = a sub-circuit's output
+    std::vector<Term> terms;
+    std::vector<Sub> subs;
+    bool boolean = true, finished = false;
+    std::string last_error;
+};
+
+namespace zk {
+
+static const uint64_t KECCAK_RC[24] = {
+    0x0000000000000001ull, 0x0000000000008082ull, 0x800000000000808aull, 0x8000000080008000ull, 0x000000000000808bull, 0x0000000080000001ull,
+    0x8000000080008081ull, 0x8000000000008009ull, 0x000000000000008aull, 0x0000000000000088ull, 0x0000000080008009ull, 0x000000008000000aull,
+    0x000000008000808bull, 0x800000000000008bull, 0x8000000000008089ull, 0x8000000000008003ull, 0x8000000000008002ull, 0x8000000000000080ull,
+    0x000000000000800aull, 0x800000008000000aull, 0x8000000080008081ull, 0x8000000000008080ull, 0x0000000080000001ull, 0x8000000080008008ull};
+static const unsigned KECCAK_RHO[24] = {1, 3, 6, 10, 15, 21, 28, 36, 45, 55, 2, 14, 27, 41, 56, 8, 25, 43, 62, 18, 39, 61, 20, 44};
+static const unsigned KECCAK_PI[24] = {10, 7, 11, 17, 18, 3, 5, 16, 8, 21, 24, 4, 15, 23, 19, 13, 12, 2, 20, 14, 22, 9, 6, 1};
+
+struct BuilderOps {
+    zk_builder& b;
+    typedef std::pair<int, uint32_t> T;   // (+1 | -1, wire)
+
+    [[noreturn]] static void fail(const std::string& m) { throw ParseError{ZK_ERR_ARG, "builder: " + m}; }
+    void live() const { if (b.finished) fail("the circuit is finished; only zk_builder_free may follow zk_builder_finish"); }
+    void known(uint32_t w) const { if (w >= b.kind.size()) fail("unknown wire id " + std::to_string(w)); }
+    uint32_t new_wire(uint8_t kind) {
+        if (b.kind.size() >= 0x7ffffff0u) fail("too many wires");
+        b.kind.push_back(kind);
+        return (uint32_t)(b.kind.size() - 1);
+    }
+    uint32_t close_sub(uint32_t l0, uint32_t r0, bool with_out, uint32_t bkind, uint32_t x, uint32_t y) {
+        if (b.subs.size() >= 0x7ffffff0u || b.terms.size() >= 0xfffffff0u) fail("too many sub-circuits");
+        const uint32_t out = with_out ? new_wire(3) : WIT_NONE;
+        b.subs.push_back({l0, r0, (uint32_t)b.terms.size(), out, bkind, x, y});
+        return out;
+    }
+    uint32_t sub(std::initializer_list<T> l, std::initializer_list<T> r, uint32_t bkind, uint32_t x, uint32_t y, bool with_out = true) {
+        const Fr one = Fr::one(), minus = -Fr::one();
+        const uint32_t l0 = (uint32_t)b.terms.size();
+        for (const T& t : l) b.terms.push_back({t.first > 0 ? one : minus, t.second});
+        const uint32_t r0 = (uint32_t)b.terms.size();
+        for (const T& t : r) b.terms.push_back({t.first > 0 ? one : minus, t.second});
+        return close_sub(l0, r0, with_out, bkind, x, y);
+    }
+    // new_sub_circuit with the caller's weights (canonical words): the circuit is no longer boolean
+    uint32_t general(const uint64_t* lw, const uint32_t* lwire, size_t nl, const uint64_t* rw, const uint32_t* rwire, size_t nr) {
+        for (size_t i = 0; i < nl; ++i) known(lwire[i]);
+        for (size_t i = 0; i < nr; ++i) known(rwire[i]);
+        for (size_t i = 0; i < nl + nr; ++i) {
+            const Fr x = fr_from_words((i < nl ? lw + 4 * i : rw + 4 * (i - nl)));
+            if (!x.raw_in_range()) throw ParseError{ZK_ERR_RANGE, "builder: weight >= r"};
+        }
+        const uint32_t l0 = (uint32_t)b.terms.size();
+        for (size_t i = 0; i < nl; ++i) b.terms.push_back({Fr::from_canonical(fr_from_words(lw + 4 * i)), lwire[i]});
+        const uint32_t r0 = (uint32_t)b.terms.size();
+        for (size_t i = 0; i < nr; ++i) b.terms.push_back({Fr::from_canonical(fr_from_words(rw + 4 * i)), rwire[i]});
+        b.boolean = false;
+        return close_sub(l0, r0, true, BOOL_NONE, 0, 0);
+    }
+
+    // ---- mod.rs:723-798, 939-950 ----
+    uint32_t bit_check(uint32_t x) { return sub({{1, x}}, {{1, x}, {-1, 1}}, BOOL_ZERO, x, x); }
+    uint32_t not_(uint32_t x) { return sub({{1, 1}}, {{1, 1}, {-1, x}}, BOOL_NOT, x, x); }
+    uint32_t and_(uint32_t x, uint32_t y) { return sub({{1, x}}, {{1, y}}, BOOL_AND, x, y); }
+    uint32_t or_(uint32_t x, uint32_t y) {
+        const uint32_t t = and_(x, y);
+        return sub({{-1, t}, {1, x}, {1, y}}, {{1, 1}}, BOOL_OR, x, y);
+    }
+    uint32_t xor_(uint32_t x, uint32_t y) { return sub({{1, x}, {-1, y}}, {{1, x}, {-1, y}}, BOOL_XOR, x, y); }
+    uint32_t nand(uint32_t x, uint32_t y) { return not_(and_(x, y)); }
+    uint32_t nor(uint32_t x, uint32_t y) {
+        const uint32_t t = and_(x, y);
+        return sub({{1, 1}, {1, t}, {-1, x}, {-1, y}}, {{1, 1}}, BOOL_NOR, x, y);
+    }
+    uint32_t xnor(uint32_t x, uint32_t y) { return sub({{1, 1}, {-1, x}, {1, y}}, {{1, 1}, {1, x}, {-1, y}}, BOOL_XNOR, x, y); }
+    uint32_t less(uint32_t x, uint32_t y) { return sub({{1, 1}, {-1, x}}, {{1, y}}, BOOL_LESS, x, y); }
+    uint32_t greater(uint32_t x, uint32_t y) { return sub({{1, 1}, {-1, y}}, {{1, x}}, BOOL_GREATER, x, y); }
+    void assert_bit(uint32_t x) { sub({{1, x}}, {{1, x}, {-1, 1}}, BOOL_NONE, x, x, false); }
+
+    uint32_t gate(int kind, uint32_t x, uint32_t y) {
+        switch (kind) {
+            case ZK_GATE_BIT_CHECK: return bit_check(x);
+            case ZK_GATE_NOT: return not_(x);
+            case ZK_GATE_AND: return and_(x, y);
+            case ZK_GATE_OR: return or_(x, y);
+            case ZK_GATE_XOR: return xor_(x, y);
+            case ZK_GATE_NAND: return nand(x, y);
+            case ZK_GATE_NOR: return nor(x, y);
+            case ZK_GATE_XNOR: return xnor(x, y);
+            case ZK_GATE_LESS: return less(x, y);
+            case ZK_GATE_GREATER: return greater(x, y);
+        }
+        fail("unknown gate kind " + std::to_string(kind));
+    }
+    static bool unary(int kind) { return kind == ZK_GATE_BIT_CHECK || kind == ZK_GATE_NOT; }
+
+    // ---- mod.rs:995-1241 ----
+    uint32_t is_equal(const uint32_t* l, const uint32_t* r, size_t n) {
+        uint32_t acc = xnor(l[0], r[0]);
+        for (size_t i = 1; i < n; ++i) {
+            const uint32_t eq = xnor(l[i], r[i]);
+            acc = and_(eq, acc);
+        }
+        return acc;
+    }
+    uint32_t is_equal_zero(const uint32_t* x, size_t n) {
+        uint32_t acc = xnor(x[0], 0);
+        for (size_t i = 1; i < n; ++i) {
+            const uint32_t eq = xnor(x[i], 0);
+            acc = and_(eq, acc);
+        }
+        return acc;
+    }
+    // one bit: the reference's fold runs fan_in over an empty list of equalities and panics; the single new_greater_than gate is the answer
+    uint32_t greater_than(const uint32_t* l, const uint32_t* r, size_t n) {
+        const uint32_t cmp0 = greater(l[0], r[0]);
+        if (n == 1) return cmp0;
+        std::vector<uint32_t> cmp, eq;
+        for (size_t i = 1; i < n; ++i) {
+            cmp.push_back(greater(l[i], r[i]));
+            eq.push_back(xnor(l[i], r[i]));
+        }
+        uint32_t acc = cmp.back();
+        cmp.pop_back();
+        cmp.insert(cmp.begin(), cmp0);
+        for (size_t k = 0; k < cmp.size(); ++k) {
+            uint32_t all_eq = eq[k];
+            for (size_t i = k + 1; i < eq.size(); ++i) all_eq = and_(all_eq, eq[i]);
+            const uint32_t both = and_(cmp[k], all_eq);
+            acc = or_(acc, both);
+        }
+        return acc;
+    }
+    uint32_t compare(int kind, const uint32_t* l, const uint32_t* r, size_t n) {
+        switch (kind) {
+            case ZK_CMP_EQUAL: return is_equal(l, r, n);
+            case ZK_CMP_EQUAL_ZERO: return is_equal_zero(l, n);
+            case ZK_CMP_GREATER: return greater_than(l, r, n);
+            case ZK_CMP_LESS: {
+                const uint32_t neg = not_(greater_than(l, r, n));
+                const uint32_t neg_eq = not_(is_equal(l, r, n));
+                return and_(neg, neg_eq);
+            }
+            case ZK_CMP_LESS_EQ: {
+                const uint32_t neg = not_(greater_than(l, r, n));
+                return or_(neg, is_equal(l, r, n));
+            }
+            case ZK_CMP_GREATER_EQ: {
+                const uint32_t gt = greater_than(l, r, n);
+                return or_(gt, is_equal(l, r, n));
+            }
+        }
+        fail("unknown comparator " + std::to_string(kind));
+    }
+
+    // ---- mod.rs:1247-1398 ----
+    typedef std::array<uint32_t, 64> Lane;   // a Word64, least significant bit first
+    static Lane rotl(const Lane& x, unsigned by) {
+        Lane o;
+        for (unsigned i = 0; i < 64; ++i) o[i] = x[(i + 64 - by % 64) % 64];
+        return o;
+    }
+    Lane xor64(const Lane& x, const Lane& y) {
+        Lane o;
+        for (unsigned i = 0; i < 64; ++i) o[i] = xor_(x[i], y[i]);
+        return o;
+    }
+    void keccak_f(Lane* a, unsigned rounds) {
+        for (unsigned rnd = 0; rnd < rounds; ++rnd) {
+            Lane col[5];
+            for (auto& c : col) c.fill(0);
+            for (unsigned x = 0; x < 5; ++x)                 // theta: column parities, folded from the zero word
+                for (unsigned y = 0; y < 25; y += 5) col[x] = xor64(col[x], a[x + y]);
+            for (unsigned x = 0; x < 5; ++x)
+                for (unsigned y = 0; y < 25; y += 5) {
+                    const Lane t = xor64(a[y + x], col[(x + 4) % 5]);
+                    a[y + x] = xor64(t, rotl(col[(x + 1) % 5], 1));
+                }
+            Lane last = a[1];                                // rho and pi: a renaming
+            for (unsigned x = 0; x < 24; ++x) {
+                const Lane keep = a[KECCAK_PI[x]];
+                a[KECCAK_PI[x]] = rotl(last, KECCAK_RHO[x]);
+                last = keep;
+            }
+            for (unsigned y = 0; y < 25; y += 5) {           // chi
+                Lane row[5];
+                for (unsigned x = 0; x < 5; ++x) row[x] = a[y + x];
+                for (unsigned x = 0; x < 5; ++x) {
+                    Lane n, c;
+                    for (unsigned i = 0; i < 64; ++i) n[i] = not_(row[(x + 1) % 5][i]);
+                    for (unsigned i = 0; i < 64; ++i) c[i] = and_(n[i], row[(x + 2) % 5][i]);
+                    a[y + x] = xor64(row[x], c);
+                }
+            }
+            Lane rc;                                         // iota
+            for (unsigned i = 0; i < 64; ++i) rc[i] = (uint32_t)((KECCAK_RC[rnd] >> i) & 1);
+            a[0] = xor64(a[0], rc);
+        }
+    }
+    void keccak(const uint32_t* in, size_t n_bytes, unsigned rate, unsigned delim, unsigned rounds, uint32_t* out, size_t out_bytes) {
+        if (rate < 1 || rate > 200) fail("keccak: rate_bytes must be in 1..200");
+        if (rounds < 1 || rounds > 24) fail("keccak: rounds must be in 1..24");
+        if (delim > 0xff) fail("keccak: delim is one byte");
+        for (size_t i = 0; i < 8 * n_bytes; ++i) known(in[i]);
+        Lane a[25];
+        for (auto& l : a) l.fill(0);
+        auto xor_byte = [&](unsigned at, const uint32_t* src) {
+            for (unsigned i = 0; i < 8; ++i) a[at / 8][8 * (at % 8) + i] = xor_(a[at / 8][8 * (at % 8) + i], src[i]);
+        };
+        unsigned offset = 0;
+        for (size_t k = 0; k < n_bytes; ++k) {
+            xor_byte(offset, in + 8 * k);
+            if (++offset == rate) { keccak_f(a, rounds); offset = 0; }
+        }
+        uint32_t cst[8];
+        for (unsigned i = 0; i < 8; ++i) cst[i] = (delim >> i) & 1;
+        xor_byte(offset, cst);
+        for (unsigned i = 0; i < 8; ++i) cst[i] = (0x80u >> i) & 1;
+        xor_byte(rate - 1, cst);
+        keccak_f(a, rounds);
+        size_t op = 0, left = out_bytes;
+        auto copy = [&](size_t count) {
+            for (size_t k = 0; k < count; ++k)
+                for (unsigned i = 0; i < 8; ++i) out[8 * (op + k) + i] = a[k / 8][8 * (k % 8) + i];
+        };
+        while (left >= rate) {
+            copy(rate);
+            keccak_f(a, rounds);
+            op += rate;
+            left -= rate;
+        }
+        copy(left);
+    }
+};
+
+// ---- finishing ------------------------------------------------------------------------------------
+// stable counting sort of operations by level; returns level_ptr (levels + 1 entries)
+template <class Op>
+static std::vector<uint32_t> sort_by_level(std::vector<Op>& ops, const std::vector<uint32_t>& op_level) {
+    uint32_t levels = 0;
+    for (uint32_t lv : op_level) levels = std::max(levels, lv);
+    std::vector<uint32_t> ptr(levels + 1, 0);
+    for (uint32_t lv : op_level) ++ptr[lv];
+    for (uint32_t l = 1; l <= levels; ++l) ptr[l] += ptr[l - 1];
+    std::vector<uint32_t> at(ptr.begin(), ptr.end());
+    std::vector<Op> sorted(ops.size());
+    for (size_t i = 0; i < ops.size(); ++i) sorted[at[op_level[i] - 1]++] = ops[i];
+    ops.swap(sorted);
+    return ptr;
+}
+
+// The sub-circuits as a zk::Tape (witgen_tape.hpp): a scaled sum is MUL by a pooled constant and ADD into fresh temporaries, a weight
+// of one reads the slot itself, an entry on the constant 1 is the pooled weight, and a side that repeats the other (XOR) is summed once.
+static void built_compile_tape(zk_circuit& c) {
+    const Built& p = *c.built;
+    Tape& t = c.tape;
+    const size_t m = c.u.size();
+    t.n_in = p.in_wit.size();
+    t.m = m;
+    t.slots = m;
+    t.in_slot = p.in_wit;
+    t.in_bit.resize(t.n_in);
+    for (size_t i = 0; i < t.n_in; ++i) t.in_bit[i] = p.in_bit[i] ? p.in_wire[i] + 1 : 0;
+    std::vector<uint32_t> slot_level(m, 0), node_level(m, 0), op_level, per_level;
+    std::map<std::array<uint32_t, 8>, uint32_t> pool;
+    auto constant = [&](const Fr& v) {
+        std::array<uint32_t, 8> key;
+        for (int i = 0; i < 8; ++i) key[i] = v.l[i];
+        auto it = pool.find(key);
+        if (it == pool.end()) { it = pool.emplace(key, (uint32_t)t.consts.size()).first; t.consts.push_back(v); }
+        return it->second | TAPE_CONST;
+    };
+    auto fresh = [&]() { slot_level.push_back(0); return (uint32_t)t.slots++; };
+    auto level_of = [&](uint32_t x) { return (x & TAPE_CONST) ? 0u : slot_level[x]; };
+    auto emit = [&](uint32_t kind, uint32_t dst, uint32_t a, uint32_t b) {
+        const uint32_t lv = 1 + std::max(level_of(a), level_of(b));
+        t.ops.push_back({dst, a, b, kind});
+        op_level.push_back(lv);
+        slot_level[dst] = lv;
+        return dst;
+    };
+    const Fr one = Fr::one();
+    auto side = [&](uint32_t from, uint32_t to) {
+        uint32_t acc = 0;
+        bool any = false;
+        for (uint32_t e = from; e < to; ++e) {
+            const BuiltTerm& x = p.terms[e];
+            uint32_t v;
+            if (x.wit == 0) v = constant(x.w);
+            else if (x.w == one) v = x.wit;
+            else v = emit(TAPE_MUL, fresh(), constant(x.w), x.wit);
+            acc = any ? emit(TAPE_ADD, fresh(), acc, v) : v;
+            any = true;
+        }
+        return any ? acc : constant(Fr::zero());
+    };
+    auto same_sides = [&](const BuiltSub& s) {
+        if (s.r0 - s.l0 != s.end - s.r0) return false;
+        for (uint32_t i = 0; i < s.r0 - s.l0; ++i)
+            if (p.terms[s.l0 + i].wit != p.terms[s.r0 + i].wit || p.terms[s.l0 + i].w != p.terms[s.r0 + i].w) return false;
+        return true;
+    };
+    for (const BuiltSub& s : p.subs) {
+        if (s.out == WIT_NONE) continue;              // an assertion computes nothing
+        uint32_t node = 0;
+        for (uint32_t e = s.l0; e < s.end; ++e) node = std::max(node, node_level[p.terms[e].wit]);
+        node_level[s.out] = ++node;
+        if (per_level.size() < node) per_level.resize(node, 0);
+        ++per_level[node - 1];
+        const uint32_t l = side(s.l0, s.r0);
+        const uint32_t r = same_sides(s) ? l : side(s.r0, s.end);
+        emit(TAPE_MUL, s.out, l, r);
+    }
+    if (t.slots >= TAPE_CONST || t.ops.size() >= TAPE_CONST) {
+        t.status = ZK_ERR_SIZE;
+        t.error = "circuit too large for the witness tape";
+        t.ops.clear(); t.consts.clear(); t.in_slot.clear(); t.in_bit.clear();
+        t.slots = 0;
+        return;
+    }
+    t.depth = per_level.size();
+    for (uint32_t n : per_level) t.width = std::max<size_t>(t.width, n);
+    t.level_ptr = sort_by_level(t.ops, op_level);
+}
+
+static zk_circuit* builder_finish(zk_builder& b, const uint32_t* verify, size_t n_verify) {
+    BuilderOps ops{b};
+    ops.live();
+    const size_t wires = b.kind.size();
+    const uint32_t UNSET = 0xfffffffeu;
+    std::vector<uint32_t> wit(wires, UNSET);
+    uint32_t next = 1;
+    for (size_t i = 0; i < n_verify; ++i) {
+        ops.known(verify[i]);
+        if (verify[i] < 2) BuilderOps::fail("verify wire " + std::to_string(verify[i]) + " is a constant");
+        if (wit[verify[i]] != UNSET) BuilderOps::fail("verify wire " + std::to_string(verify[i]) + " is named twice");
+        wit[verify[i]] = next++;
+    }
+    for (size_t w = 2; w < wires; ++w)
+        if ((b.kind[w] == 1 || b.kind[w] == 2) && wit[w] == UNSET) wit[w] = next++;
+    for (size_t w = 2; w < wires; ++w)
+        if (wit[w] == UNSET) wit[w] = next++;
+    wit[0] = WIT_NONE;   // the constant zero: no witness wire, its entries are dropped
+    wit[1] = 0;
+    const size_t m = next;
+
+    std::unique_ptr<zk_circuit> c(new zk_circuit());
+    c->u.resize(m); c->v.resize(m); c->w.resize(m);
+    c->input = n_verify;
+    c->n_gates = b.subs.size();
+    c->built.reset(new Built());
+    Built& p = *c->built;
+    const Fr one = Fr::one();
+    p.subs.reserve(b.subs.size());
+    p.terms.reserve(b.terms.size());
+    for (size_t k = 0; k < b.subs.size(); ++k) {
+        const zk_builder::Sub& s = b.subs[k];
+        BuiltSub o;
+        o.l0 = (uint32_t)p.terms.size();
+        for (uint32_t e = s.l0; e < s.r0; ++e) {
+            const uint32_t x = wit[b.terms[e].wire];
+            if (x == WIT_NONE) continue;
+            p.terms.push_back({b.terms[e].w, x});
+            c->u[x].push_back({(uint32_t)k, b.terms[e].w});
+        }
+        o.r0 = (uint32_t)p.terms.size();
+        for (uint32_t e = s.r0; e < s.end; ++e) {
+            const uint32_t x = wit[b.terms[e].wire];
+            if (x == WIT_NONE) continue;
+            p.terms.push_back({b.terms[e].w, x});
+            c->v[x].push_back({(uint32_t)k, b.terms[e].w});
+        }
+        o.end = (uint32_t)p.terms.size();
+        o.out = s.out == WIT_NONE ? WIT_NONE : wit[s.out];
+        if (o.out != WIT_NONE) c->w[o.out].push_back({(uint32_t)k, one});
+        p.subs.push_back(o);
+    }
+    p.boolean = b.boolean;
+    p.wire_wit = wit;
+    for (size_t w = 2; w < wires; ++w)
+        if (b.kind[w] == 1 || b.kind[w] == 2) {
+            p.in_wit.push_back(wit[w]);
+            p.in_wire.push_back((uint32_t)w);
+            p.in_bit.push_back(b.kind[w] == 1);
+            if (b.kind[w] == 2) p.boolean = false;
+        }
+    if (p.boolean) {
+        // witness index m stands for the constant 0
+        auto idx = [&](uint32_t wire) { return wit[wire] == WIT_NONE ? (uint32_t)m : wit[wire]; };
+        std::vector<uint32_t> level(m + 1, 0), op_level;
+        for (const zk_builder::Sub& s : b.subs) {
+            if (s.out == WIT_NONE) continue;
+            const BoolOp op{wit[s.out], idx(s.a), idx(s.b), s.bkind};
+            const uint32_t lv = 1 + std::max(level[op.a], level[op.b]);
+            level[op.dst] = lv;
+            p.bool_ops.push_back(op);
+            op_level.push_back(lv);
+        }
+        p.bool_level_ptr = sort_by_level(p.bool_ops, op_level);
+    }
+    built_compile_tape(*c);
+    b.finished = true;
+    b.terms.clear(); b.terms.shrink_to_fit();
+    b.subs.clear(); b.subs.shrink_to_fit();
+    return c.release();
+}
+
+// ---- the two host evaluators ----------------------------------------------------------------------
+// inputs of a built circuit: canonical words < r, and 0 or 1 where the wire was made as a bit
+static void built_check_inputs(const Tape& t, const uint64_t* inputs, size_t n_in) {
+    for (size_t i = 0; i < n_in; ++i)
+        if (!fr_from_words(inputs + 4 * i).raw_in_range()) throw ParseError{ZK_ERR_RANGE, "input value >= r"};
+    for (size_t i = 0; i < n_in && i < t.in_bit.size(); ++i)
+        if (t.in_bit[i] && (inputs[4 * i] > 1 || inputs[4 * i + 1] || inputs[4 * i + 2] || inputs[4 * i + 3]))
+            throw ParseError{ZK_ERR_RANGE, bit_input_error(0, i, t.in_bit[i] - 1)};
+}
+// the sub-circuits in creation order: what the reference's memoised `evaluate` (mod.rs:559-595) computes for every wire
+static void built_weights(const zk_circuit& c, const uint64_t* inputs, size_t n_in, uint64_t* out, size_t m) {
+    const Built& p = *c.built;
+    auto serr = [](const std::string& s) { return ParseError{ZK_ERR_ARG, "StructureErr(None, " + s + ")"}; };
+    if (p.in_wit.size() != n_in) throw serr("Wrong number of values supplied");
+    if (m != c.u.size()) throw serr("weights buffer size mismatch");
+    built_check_inputs(c.tape, inputs, n_in);
+    std::vector<Fr> vals(m, Fr::zero());
+    vals[0] = Fr::one();
+    for (size_t i = 0; i < n_in; ++i) vals[p.in_wit[i]] = Fr::from_canonical(fr_from_words(inputs + 4 * i));
+    for (const BuiltSub& s : p.subs) {
+        if (s.out == WIT_NONE) continue;
+        Fr l = Fr::zero(), r = Fr::zero();
+        for (uint32_t e = s.l0; e < s.r0; ++e) l = l + p.terms[e].w * vals[p.terms[e].wit];
+        for (uint32_t e = s.r0; e < s.end; ++e) r = r + p.terms[e].w * vals[p.terms[e].wit];
+        vals[s.out] = l * r;
+    }
+    for (size_t i = 0; i < m; ++i) fr_to_words(vals[i].to_canonical(), out + 4 * i);
+}
+
+}  // namespace zk

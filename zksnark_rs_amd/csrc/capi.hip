@@ -144,6 +144,9 @@ static long* option_slot(zk_ctx* ctx, const char* key) {
     if (!std::strcmp(key, "powers_mul_ppl")) return &ctx->opt_powers_mul_ppl;
     if (!std::strcmp(key, "merge_lh")) return &ctx->opt_merge_lh;
     if (!std::strcmp(key, "witgen_scratch_kib")) return &ctx->opt_witgen_scratch_kib;
+    if (!std::strcmp(key, "boolgen_scratch_kib")) return &ctx->opt_boolgen_scratch_kib;
+    if (!std::strcmp(key, "boolgen_group_words")) return &ctx->opt_boolgen_group_words;
+    if (!std::strcmp(key, "boolgen_expand_form")) return &ctx->opt_boolgen_expand_form;
     if (!std::strcmp(key, "vk_table_kib")) return &ctx->opt_vk_table_kib;
     if (!std::strcmp(key, "qap_check_chunk")) return &ctx->opt_qap_check_chunk;
     if (!std::strcmp(key, "qap_check_by_instance")) return &ctx->opt_qap_check_by_instance;

@@ -139,6 +139,9 @@ struct zk_ctx {
     long opt_tail_stream = 0;     // merged L + H product: its reduction tail on the idle L stream (measurement switch)
     long opt_ntt_fuse = 1;        // roots-of-unity form, two-pass sizes: element-wise kernels folded into the DIF tile loads / stores (ntt_dif_fused); measurement switch
     long opt_witgen_scratch_kib = 8L << 20;   // zk_witgen_create: cap of the slot scratch a generator keeps in HBM, KiB (8 GiB); groups of 64 instances run in chunks under it
+    long opt_boolgen_scratch_kib = 4L << 20;  // zk_boolgen_create: cap of the packed wire state a generator keeps in HBM, KiB (4 GiB); words of 64 instances run in chunks under it
+    long opt_boolgen_group_words = 0;         // zk_boolgen_create: 64-instance words one workgroup of k_bool_eval owns (1, 2, 4, 8); 0 = the rule of boolgen.hip
+    long opt_boolgen_expand_form = 0;         // zk_boolgen_create: k_bool_expand with 0 = a lane per wire (two 16-byte stores per instance), 1 = a lane pair per wire (one store each, 1 KiB contiguous per wave instruction); same bytes, the A/B of tools/time_boolgen.py
     long opt_vk_table_kib = 65536;    // zk_vk_*: a verifying key builds its input-sum tables (60 KiB per input) only while they fit in this many KiB; a memory condition, never a verdict's (vk_batch.hip)
     long opt_qap_check_chunk = (long)ZK_QAP_CHECK_CHUNK_LANES;   // zk_qap_check*: (instance, gate) pairs per launch (qap_check.hip)
     long opt_qap_check_by_instance = 0;   // zk_qap_check*: 1 = consecutive lanes take the same gate of consecutive instances (the A/B of DESIGN 4h)

@@ -18,7 +18,7 @@
 #include <sstream>
 #include <unordered_map>
 #include "pipeline.hpp"
-#include "witgen_tape.hpp"
+#include "builder.hpp"
 
 namespace zk {
 
@@ -34,21 +34,10 @@ static bool fr_parse_decimal(const std::string& s, Fr& out) {
     return true;
 }
 
-struct ParseError {
-    int status;
-    std::string msg;
-};
-
 enum class Kw { In, Out, Verify, Program, Equal, Mul, Add };
 struct Tok {
     enum Kind { Keyword, Var, Open, Close, Literal } kind;
     Kw kw{};
-    std::string var;
-    Fr lit{};
-};
-struct Node {
-    enum Kind { In, Out, Verify, Program, Assign, Mul, Add, Var, Literal } kind;
-    std::vector<Node> kids;
     std::string var;
     Fr lit{};
 };
@@ -174,17 +163,6 @@ static std::vector<Node> parse_top(const std::vector<Tok>& toks) {
 }
 
 }  // namespace zk
-
-// DummyRep (dummy_rep.rs:6-13) for Fr + what circuit::weights needs
-struct zk_circuit {
-    typedef std::vector<std::pair<uint32_t, zk::Fr>> Row;   // (gate index 0-based, value in Montgomery form)
-    std::vector<Row> u, v, w;
-    size_t n_gates = 0, input = 0;
-    std::vector<zk::Node> exprs;
-    std::vector<std::string> order;    // variable_order (ast.rs:62-83)
-    std::string last_error;
-    zk::Tape tape;                     // circuit::weights compiled once (witgen_tape.hpp), or its static error
-};
 
 namespace zk {
 
@@ -416,6 +394,7 @@ static bool eval_node(const Node& e, const std::unordered_map<std::string, Fr>& 
 
 // circuit::weights (circuit/mod.rs:529-637): inputs in `in` order -> [1] ++ values in variable order
 static void circuit_weights(const zk_circuit& c, const uint64_t* inputs, size_t n_in, uint64_t* out, size_t m) {
+    if (c.built) return built_weights(c, inputs, n_in, out, m);   // a built circuit: its sub-circuits in creation order (builder.hpp)
     auto serr = [](const std::string& s) { return ParseError{ZK_ERR_ARG, "StructureErr(None, " + s + ")"}; };
     const auto& ex = c.exprs;
     if (ex[0].kids.size() != n_in) throw serr("Wrong number of values supplied");
@@ -454,8 +433,7 @@ static void circuit_weights_tape(const zk_circuit& c, const uint64_t* inputs, si
     const Tape& t = c.tape;
     if (t.n_in != n_in) throw serr("Wrong number of values supplied");
     if (m != t.m) throw serr("weights buffer size mismatch");
-    for (size_t i = 0; i < n_in; ++i)
-        if (!fr_from_words(inputs + 4 * i).raw_in_range()) throw ParseError{ZK_ERR_RANGE, "input value >= r"};
+    built_check_inputs(t, inputs, n_in);   // < r; 0 or 1 on the bit inputs of a built circuit
     if (t.status) throw ParseError{t.status, t.error};
     static thread_local std::vector<Fr> vals;
     if (vals.size() < t.slots) vals.resize(t.slots);
@@ -563,7 +541,7 @@ static zk_qap* circuit_to_qap(zk_ctx* ctx, const zk_circuit& c) {
 
 // The same QAP without the interpolation: the root representation's rows go to the device as they are and the prover works on
 // the integer roots 1..n in the evaluation basis (aproots.hip).  No 16384-gate limit; proofs are byte-identical to the dense form's.
-static zk_qap* circuit_to_qap_sparse(zk_ctx* ctx, const zk_circuit& c) {
+static zk_qap* circuit_to_qap_sparse(zk_ctx* ctx, const zk_circuit& c, bool unity = false) {
     const size_t n = c.n_gates, m = c.u.size();
     ZK_REQUIRE(n >= 1, ZK_ERR_ARG, "circuit has no gates");
     struct HostRows { std::vector<uint64_t> ptr, val; std::vector<uint32_t> gate; };
@@ -586,6 +564,10 @@ static zk_qap* circuit_to_qap_sparse(zk_ctx* ctx, const zk_circuit& c) {
     d.u = {h[0].ptr.data(), h[0].gate.data(), h[0].val.data()};
     d.v = {h[1].ptr.data(), h[1].gate.data(), h[1].val.data()};
     d.w = {h[2].ptr.data(), h[2].gate.data(), h[2].val.data()};
+    if (unity) {
+        while (((size_t)1 << d.log_n) < n) ++d.log_n;
+        return qap_upload_sparse(ctx, d);
+    }
     return qap_upload_sparse_integers(ctx, d, n);
 }
 
@@ -634,7 +616,7 @@ int zk_circuit_dims(const zk_circuit* c, size_t* m, size_t* n, size_t* input, si
     if (m) *m = c->u.size();
     if (n) *n = c->n_gates;
     if (input) *input = c->input;
-    if (n_in) *n_in = c->exprs[0].kids.size();
+    if (n_in) *n_in = c->built ? c->built->in_wit.size() : c->exprs[0].kids.size();
     return ZK_OK;
 }
 // which: 0 = u, 1 = v, 2 = w.  ptr has m+1 entries; gate/val receive nnz entries (pass NULL to query nnz).
@@ -693,6 +675,18 @@ int zk_circuit_qap_sparse(zk_ctx* ctx, const zk_circuit* c, zk_qap** out) {
     if (!ctx || !c || !out) return ZK_ERR_ARG;
     *out = nullptr;
     return guarded(ctx, [&] { *out = circuit_to_qap_sparse(ctx, *c); });
+}
+// the same rows at the roots of unity: gate k at w^k, n padded to a power of two by empty gates (zk_qap_upload_sparse)
+int zk_circuit_qap_sparse_unity(zk_ctx* ctx, const zk_circuit* c, zk_qap** out) {
+    if (!ctx || !c || !out) return ZK_ERR_ARG;
+    *out = nullptr;
+    return guarded(ctx, [&] { *out = circuit_to_qap_sparse(ctx, *c, true); });
+}
+int zk_circuit_is_boolean(const zk_circuit* c) { return c && c->built && c->built->boolean ? 1 : 0; }
+int zk_circuit_wire_index(const zk_circuit* c, uint32_t wire, size_t* index) {
+    if (!c || !index || !c->built || wire >= c->built->wire_wit.size() || c->built->wire_wit[wire] == WIT_NONE) return ZK_ERR_ARG;
+    *index = c->built->wire_wit[wire];
+    return ZK_OK;
 }
 int zk_qap_download_dense(zk_ctx* ctx, const zk_qap* qap, uint64_t* u, uint64_t* v, uint64_t* w, uint64_t* t) {
     if (!ctx || !qap) return ZK_ERR_ARG;

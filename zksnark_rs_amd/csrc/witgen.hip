@@ -14,7 +14,7 @@
 // Lanes behind `count` in the last group never return early: they take part in every barrier and are predicated off every load and
 // store.  Groups run in chunks of as many as the scratch cap holds (option "witgen_scratch_kib"), so `count` is not bounded by memory.
 #include "pipeline.hpp"
-#include "witgen_tape.hpp"
+#include "circuit.hpp"
 
 struct zk_witgen {
     zk_ctx* ctx = nullptr;
@@ -25,6 +25,8 @@ struct zk_witgen {
     zk::DevBuf<uint32_t> level_ptr, in_slot;
     zk::DevBuf<zk::Fr> consts, scratch;
     zk::DevBuf<unsigned long long> flag;
+    std::vector<uint32_t> h_in_bit;         // a built circuit's bit inputs (Tape::in_bit); empty for a parsed program
+    zk::DevBuf<uint32_t> in_bit;
 };
 
 namespace zk {
@@ -123,6 +125,18 @@ k_witgen(const TapeOp* __restrict__ ops, const uint32_t* __restrict__ level_ptr,
     }
 }
 
+// A built circuit's bit inputs: any value other than 0 or 1 records the lowest (instance * n_in + input).  A pass of its own in front
+// of k_witgen, launched only for circuits that have such inputs.
+__global__ void __launch_bounds__(256)
+k_witgen_bits(const uint64_t* __restrict__ inputs, const uint32_t* __restrict__ in_bit, unsigned n_in, size_t count, unsigned long long* __restrict__ flag) {
+    const size_t total = count * (size_t)n_in;
+    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
+        if (!in_bit[idx % n_in]) continue;
+        const uint64_t* x = inputs + 4 * idx;
+        if (x[0] > 1 || x[1] || x[2] || x[3]) atomicMin(flag, (unsigned long long)idx);
+    }
+}
+
 static zk_witgen* witgen_create(zk_ctx* ctx, const Tape& t) {
     ZK_REQUIRE(!t.status, t.status, t.error);
     ZK_REQUIRE(t.n_in < (1u << 31) && t.m < (1u << 31), ZK_ERR_SIZE, "witgen: program too large");
@@ -141,7 +155,9 @@ static zk_witgen* witgen_create(zk_ctx* ctx, const Tape& t) {
     up(w->consts, t.consts);
     const std::vector<uint32_t> lp = t.level_ptr.empty() ? std::vector<uint32_t>{0} : t.level_ptr;
     up(w->level_ptr, lp);
-    w->flag.alloc(1);
+    w->flag.alloc(2);
+    w->h_in_bit = t.in_bit;
+    if (!t.in_bit.empty()) up(w->in_bit, t.in_bit);
     ZK_HIP(hipStreamSynchronize(st));   // the host vectors may go away with the circuit
     return w.release();
 }
@@ -156,8 +172,14 @@ static void witgen_run(zk_witgen& w, const void* d_inputs, size_t count, void* d
                                           " KiB of scratch, more than the option witgen_scratch_kib allows");
     const size_t chunk = std::min(std::min(groups, fit), (size_t)1 << 30);
     w.scratch.ensure(chunk * w.slots * WG_LANES);
-    const unsigned long long none = WG_NO_ERROR;
-    ZK_HIP(hipMemcpyAsync(w.flag.p, &none, sizeof(none), hipMemcpyHostToDevice, st));
+    const unsigned long long none[2] = {WG_NO_ERROR, WG_NO_ERROR};
+    ZK_HIP(hipMemcpyAsync(w.flag.p, none, sizeof(none), hipMemcpyHostToDevice, st));
+    if (!w.h_in_bit.empty()) {
+        const size_t total = count * w.n_in;
+        hipLaunchKernelGGL(k_witgen_bits, dim3((unsigned)std::min<size_t>((total + 255) / 256, 65536)), dim3(256), 0, st, (const uint64_t*)d_inputs,
+                           w.in_bit.p, (unsigned)w.n_in, count, w.flag.p + 1);
+        ZK_HIP(hipGetLastError());
+    }
     for (size_t g0 = 0; g0 < groups; g0 += chunk) {      // same stream: a chunk starts when the one before has left the scratch
         const size_t g = std::min(chunk, groups - g0);
         ProfScope ps(ctx, "witgen", 0.0);
@@ -166,10 +188,12 @@ static void witgen_run(zk_witgen& w, const void* d_inputs, size_t count, void* d
                            (uint64_t*)d_out, w.flag.p);
         ZK_HIP(hipGetLastError());
     }
-    unsigned long long bad = WG_NO_ERROR;
-    ZK_HIP(hipMemcpyAsync(&bad, w.flag.p, sizeof(bad), hipMemcpyDeviceToHost, st));
+    unsigned long long bad[2] = {WG_NO_ERROR, WG_NO_ERROR};
+    ZK_HIP(hipMemcpyAsync(bad, w.flag.p, sizeof(bad), hipMemcpyDeviceToHost, st));
     ZK_HIP(hipStreamSynchronize(st));
-    ZK_REQUIRE(bad == WG_NO_ERROR, ZK_ERR_RANGE, "witgen: input value >= r in instance " + std::to_string(bad));
+    ZK_REQUIRE(bad[0] == WG_NO_ERROR, ZK_ERR_RANGE, "witgen: input value >= r in instance " + std::to_string(bad[0]));
+    ZK_REQUIRE(bad[1] == WG_NO_ERROR, ZK_ERR_RANGE,
+               "witgen: " + bit_input_error(bad[1] / w.n_in, bad[1] % w.n_in, w.h_in_bit[bad[1] % w.n_in] - 1));
 }
 
 }  // namespace zk

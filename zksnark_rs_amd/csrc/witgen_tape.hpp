@@ -34,6 +34,7 @@ struct Tape {
     size_t n_in = 0, m = 0, slots = 0;
     size_t depth = 0, width = 0;          // shape of the program with each `=` as one node (zk_circuit_tape_dims)
     std::vector<uint32_t> in_slot;        // slot of input i (every input owns one, read or not: all are range-checked)
+    std::vector<uint32_t> in_bit;         // built circuits only (else empty): 1 + the builder's wire id where input i must be 0 or 1, 0 where any field element
     std::vector<TapeOp> ops;              // sorted by level
     std::vector<uint32_t> level_ptr;      // levels + 1 entries
     std::vector<Fr> consts;
