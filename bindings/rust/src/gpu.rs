@@ -191,14 +191,18 @@ extern "C" {
     fn zk_builder_keccak(b: *mut ZkBuilder, in_wires: *const u32, n_bytes: usize, rate_bytes: c_uint, delim: c_uint, rounds: c_uint,
                          out_wires: *mut u32, out_bytes: usize) -> c_int;
     fn zk_builder_assert_bit(b: *mut ZkBuilder, wire: u32) -> c_int;
+    fn zk_builder_pack(b: *mut ZkBuilder, bits: *const u32, n_bits: usize, out: *mut u32) -> c_int;
     fn zk_builder_finish(b: *mut ZkBuilder, verify_wires: *const u32, n_verify: usize, out: *mut *mut ZkCircuit) -> c_int;
     fn zk_circuit_is_boolean(c: *const ZkCircuit) -> c_int;
+    fn zk_circuit_packed_wires(c: *const ZkCircuit, count: *mut usize) -> c_int;
     fn zk_circuit_wire_index(c: *const ZkCircuit, wire: u32, index: *mut usize) -> c_int;
     fn zk_circuit_qap_sparse_unity(ctx: *mut ZkCtx, c: *const ZkCircuit, out: *mut *mut ZkQap) -> c_int;
     fn zk_boolgen_create(ctx: *mut ZkCtx, c: *const ZkCircuit, out: *mut *mut ZkBoolgen) -> c_int;
     fn zk_boolgen_free(g: *mut ZkBoolgen);
     fn zk_boolgen_run(g: *mut ZkBoolgen, d_in_bits: *const c_void, in_stride_bytes: usize, count: usize, d_weights_out: *mut c_void,
                       m: usize) -> c_int;
+    fn zk_boolgen_eval_fields(g: *mut ZkBoolgen, d_in_bits: *const c_void, in_stride_bytes: usize, count: usize, wires: *const u32, n_wires: usize,
+                              d_out_words: *mut c_void) -> c_int;
     fn zk_boolgen_eval(g: *mut ZkBoolgen, d_in_bits: *const c_void, in_stride_bytes: usize, count: usize, wires: *const u32, n_wires: usize,
                        d_out_bits: *mut c_void, out_stride_bytes: usize) -> c_int;
     // does a witness satisfy the QAP (sparse forms)?  One witness on the host, or `count` of them where zk_witgen_run left them
@@ -1266,6 +1270,12 @@ impl GpuCircuitBuilder {
     pub fn new_nor(&mut self, x: WireId, y: WireId) -> WireId { self.gate(Gate::Nor, x, y) }
     pub fn new_xnor(&mut self, x: WireId, y: WireId) -> WireId { self.gate(Gate::Xnor, x, y) }
     pub fn assert_bit(&mut self, w: WireId) { self.ok(unsafe { zk_builder_assert_bit(self.0, w) }) }
+    /// the packed wire sum 2^i bits[i] over 1..253 wires, least significant first: one sub-circuit, a field element (not in the reference)
+    pub fn pack(&mut self, bits: &[WireId]) -> WireId {
+        let mut out = 0u32;
+        self.ok(unsafe { zk_builder_pack(self.0, bits.as_ptr(), bits.len(), &mut out) });
+        out
+    }
     pub fn fan_in(&mut self, inputs: &[WireId], g: Gate) -> WireId {
         let mut out = 0u32;
         self.ok(unsafe { zk_builder_fan_in(self.0, g as c_int, inputs.as_ptr(), inputs.len(), &mut out) });
@@ -1312,6 +1322,11 @@ impl GpuCircuitBuilder {
 
 impl BuiltCircuit {
     pub fn is_boolean(&self) -> bool { unsafe { zk_circuit_is_boolean(self.0) == 1 } }
+    pub fn packed_wires(&self) -> usize {
+        let mut n = 0usize;
+        unsafe { zk_circuit_packed_wires(self.0, &mut n) };
+        n
+    }
     pub fn wire_index(&self, wire: WireId) -> Option<usize> {
         let mut i = 0usize;
         if unsafe { zk_circuit_wire_index(self.0, wire, &mut i) } == 0 { Some(i) } else { None }
@@ -1345,6 +1360,10 @@ impl Boolgen {
     }
     pub fn eval(&self, d_in_bits: *const c_void, in_stride_bytes: usize, count: usize, wires: &[u32], d_out_bits: *mut c_void, out_stride_bytes: usize) {
         unsafe { check(self.ctx, zk_boolgen_eval(self.g, d_in_bits, in_stride_bytes, count, wires.as_ptr(), wires.len(), d_out_bits, out_stride_bytes)) }
+    }
+    /// bit and packed wires alike as 4 canonical words each: with wires = 1..l the `inputs` of zk_verify_batch
+    pub fn eval_fields(&self, d_in_bits: *const c_void, in_stride_bytes: usize, count: usize, wires: &[u32], d_out_words: *mut c_void) {
+        unsafe { check(self.ctx, zk_boolgen_eval_fields(self.g, d_in_bits, in_stride_bytes, count, wires.as_ptr(), wires.len(), d_out_words)) }
     }
 }
 

@@ -331,7 +331,7 @@ int zk_witgen_run(zk_witgen* w, const void* d_inputs, size_t n_in, size_t count,
  *     there, so its entries are dropped from every sub-circuit at zk_builder_finish (they contribute 0 either way);
  *   - the reference's builder -> DummyRep conversion prepends num_wires empty rows and is not reproduced: sub-circuit k
  *     is gate k;
- *   - zk_builder_assert_bit exists (see there). */
+ *   - zk_builder_assert_bit and zk_builder_pack exist (see there). */
 typedef struct zk_builder zk_builder;
 #define ZK_WIRE_ZERO 0u
 #define ZK_WIRE_ONE 1u
@@ -388,6 +388,16 @@ int zk_builder_keccak(zk_builder* b, const uint32_t* in_wires, size_t n_bytes, u
 /* The gate w (w - 1) = 0 with NO output wire (an empty W entry).  The reference's bit checker only produces an unconstrained wire,
  * so without this call a verifier has no way to force an input to be 0 or 1. */
 int zk_builder_assert_bit(zk_builder* b, uint32_t wire);
+/* out = sum_i 2^i * bits[i], as ONE sub-circuit (sum 2^i bits[i]) * (1) = out.  1 <= n_bits <= ZK_PACK_MAX_BITS (253), so the sum of
+ * 0/1 operands is < 2^253 < r and distinct bit strings give distinct elements.  Operands may be any known wire, ZK_WIRE_ONE (adds 2^i)
+ * and ZK_WIRE_ZERO (dropped at finish, like everywhere) included, and a wire may occur at several positions.  n_bits of 0 or above
+ * 253: ZK_ERR_ARG with text.  The output is a PACKED wire: an ordinary witness index, a field element instead of a bit; it may be a
+ * verify wire -- a 256-bit digest is then two public inputs of 128 bits instead of 256.  The circuit stays bit-sliceable
+ * (zk_circuit_is_boolean) iff every pack operand is a constant, a ZK_WIRE_BIT input or the output of a gate, comparator or sponge
+ * sub-circuit, and no packed wire is an operand of anything; a packed wire fed into a gate, another pack, zk_builder_assert_bit, a
+ * comparator or the sponge is legal and sends the circuit to the tape (zk_witgen_*), as zk_builder_sub_circuit does. */
+#define ZK_PACK_MAX_BITS 253
+int zk_builder_pack(zk_builder* b, const uint32_t* bits, size_t n_bits, uint32_t* out);
 /* The circuit as an ordinary zk_circuit (free it with zk_circuit_free; the builder may be freed before or after).  Witness order: the
  * constant 1, the verify wires in the order given (qap.input = n_verify), the remaining input wires in creation order, the remaining
  * wires by id.  Sub-circuit k is gate k (0-based), at root k + 1 of zk_circuit_qap / _qap_sparse.  ZK_ERR_ARG with text: a verify wire
@@ -396,9 +406,12 @@ int zk_builder_assert_bit(zk_builder* b, uint32_t wire);
  * zk_witgen_run a tape compiled from them; n_in is the number of input wires, inputs are field elements in creation order, and a
  * value other than 0 or 1 on a ZK_WIRE_BIT input is ZK_ERR_RANGE with instance, input and wire named. */
 int zk_builder_finish(zk_builder* b, const uint32_t* verify_wires, size_t n_verify, zk_circuit** out);
-/* 1: every input is a bit wire and every sub-circuit came from a gate, a comparator, the sponge or zk_builder_assert_bit, so
- * zk_boolgen_create takes the circuit; 0: anything else, every parsed circuit included */
+/* 1: zk_boolgen_create takes the circuit -- every input is a bit wire and every sub-circuit came from a gate, a comparator, the sponge,
+ * zk_builder_assert_bit or a zk_builder_pack over bit-valued wires whose output nothing reads (see there); 0: anything else, every
+ * parsed circuit included */
 int zk_circuit_is_boolean(const zk_circuit* c);
+/* *count = the number of packed wires (zk_builder_pack calls); 0 for parsed circuits and for built circuits without packs */
+int zk_circuit_packed_wires(const zk_circuit* c, size_t* count);
 /* witness index of a builder wire in a built circuit (ZK_WIRE_ONE -> 0).  ZK_ERR_ARG: a parsed circuit, an unknown id, ZK_WIRE_ZERO. */
 int zk_circuit_wire_index(const zk_circuit* c, uint32_t wire, size_t* index);
 /* The circuit's rows through zk_qap_upload_sparse: gate k at w^k, n padded to the next power of two by empty gates (t = x^n - 1).  For
@@ -425,9 +438,15 @@ int zk_boolgen_run(zk_boolgen* g, const void* d_in_bits, size_t in_stride_bytes,
 /* The same evaluation, returning only the named witness indices, packed as the inputs are: wire wires[i] of instance j is bit i % 8
  * of the byte i / 8 at d_out_bits + j * out_stride_bytes (unused bits of the last byte are 0, bytes behind it untouched).  This is how
  * a caller gets a digest -- the public inputs -- without 32 bytes per wire.  wires is a host array of witness indices < m.
- * Errors as zk_boolgen_run; out_stride_bytes < ceil(n_wires / 8) or an index >= m: ZK_ERR_ARG. */
+ * Errors as zk_boolgen_run; out_stride_bytes < ceil(n_wires / 8), an index >= m or the index of a packed wire (no bit: use
+ * zk_boolgen_eval_fields): ZK_ERR_ARG. */
 int zk_boolgen_eval(zk_boolgen* g, const void* d_in_bits, size_t in_stride_bytes, size_t count, const uint32_t* wires, size_t n_wires,
                     void* d_out_bits, size_t out_stride_bytes);
+/* wires[i] (witness indices < m, bit wires and packed wires alike) of instance j -> 4 canonical words at
+ * d_out_words + (j * n_wires + i) * 4: with wires = 1..l this is exactly the `inputs` array of zk_verify_batch / zk_vk_verify_batch.
+ * Nothing else is written.  Errors as zk_boolgen_eval. */
+int zk_boolgen_eval_fields(zk_boolgen* g, const void* d_in_bits, size_t in_stride_bytes, size_t count, const uint32_t* wires,
+                           size_t n_wires, void* d_out_words);
 
 /* ------------------------------------------------------------------------------------------
  * CRS  (SigmaG1 / SigmaG2, groth16/mod.rs:105-121)

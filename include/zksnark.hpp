@@ -118,6 +118,7 @@ class Circuit {
     const zk_circuit* get() const { return c_; }
     static Circuit adopt(zk_circuit* c) { return Circuit(c); }   // takes ownership (builder::Circuit::finish)
     bool is_boolean() const { return zk_circuit_is_boolean(c_) != 0; }
+    size_t packed_wires() const { size_t n = 0; zk_circuit_packed_wires(c_, &n); return n; }   // builder::Circuit::pack calls
     // witness index of a builder wire (built circuits; the constant-zero wire has none)
     size_t wire_index(uint32_t wire) const {
         size_t i = 0;
@@ -311,6 +312,10 @@ class Circuit {
     WireId new_xnor(WireId x, WireId y) { return gate(Gate::Xnor, x, y); }
     // w (w - 1) = 0 without output wire: what forces an input to be 0 or 1 (not in the reference)
     void assert_bit(WireId w) { check(zk_builder_assert_bit(b_, w)); }
+    // the packed wire sum 2^i bits[i] over 1..ZK_PACK_MAX_BITS wires, least significant first: one sub-circuit whose output is a field
+    // element (not in the reference); a 32-byte digest is two of them as verify wires instead of 256 bits
+    template <class Wires>
+    WireId pack(const Wires& bits) { WireId o; check(zk_builder_pack(b_, bits.data(), bits.size(), &o)); return o; }
 
     template <class Wires>
     WireId fan_in(const Wires& inputs, Gate g) { WireId o; check(zk_builder_fan_in(b_, (int)g, inputs.data(), inputs.size(), &o)); return o; }
@@ -396,6 +401,10 @@ class Boolgen {
     void eval(const void* d_in_bits, size_t in_stride_bytes, size_t count, const std::vector<uint32_t>& wires, void* d_out_bits,
               size_t out_stride_bytes) const {
         c_.check(zk_boolgen_eval(g_, d_in_bits, in_stride_bytes, count, wires.data(), wires.size(), d_out_bits, out_stride_bytes), "Boolgen::eval");
+    }
+    // bit and packed wires alike as 4 canonical words each: with wires = 1..l the `inputs` of zk_verify_batch
+    void eval_fields(const void* d_in_bits, size_t in_stride_bytes, size_t count, const std::vector<uint32_t>& wires, void* d_out_words) const {
+        c_.check(zk_boolgen_eval_fields(g_, d_in_bits, in_stride_bytes, count, wires.data(), wires.size(), d_out_words), "Boolgen::eval_fields");
     }
 
    private:

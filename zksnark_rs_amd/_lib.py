@@ -176,14 +176,17 @@ SIGNATURES = {
     "zk_builder_compare": (C.c_int, [C.c_void_p, C.c_int, u32p, u32p, C.c_size_t, u32p]),
     "zk_builder_keccak": (C.c_int, [C.c_void_p, u32p, C.c_size_t, C.c_uint, C.c_uint, C.c_uint, u32p, C.c_size_t]),
     "zk_builder_assert_bit": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "zk_builder_pack": (C.c_int, [C.c_void_p, u32p, C.c_size_t, u32p]),
     "zk_builder_finish": (C.c_int, [C.c_void_p, u32p, C.c_size_t, C.POINTER(C.c_void_p)]),
     "zk_circuit_is_boolean": (C.c_int, [C.c_void_p]),
+    "zk_circuit_packed_wires": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t)]),
     "zk_circuit_wire_index": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_size_t)]),
     "zk_circuit_qap_sparse_unity": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
     "zk_boolgen_create": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
     "zk_boolgen_free": (None, [C.c_void_p]),
     "zk_boolgen_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t]),
     "zk_boolgen_eval": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, u32p, C.c_size_t, C.c_void_p, C.c_size_t]),
+    "zk_boolgen_eval_fields": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, u32p, C.c_size_t, C.c_void_p]),
     "zk_msm_auto_window": (C.c_int, [C.c_size_t]),
     "zk_msm_auto_window_g2": (C.c_int, [C.c_size_t]),
     "zk_circuit_qap": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),

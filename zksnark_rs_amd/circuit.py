@@ -8,7 +8,9 @@
 and its gate-level circuit builder (circuit/builder/mod.rs, types.rs; host code as well):
 
     Circuit<T>, new_word8 .. keccak256, validate_order       -> Builder, whose finish() is an ordinary Circuit
-    bit-sliced witnesses of a boolean built circuit          -> Boolgen(ctx, circuit).run(...) / .eval(...) (csrc/boolgen.hip)
+    bit-sliced witnesses of a boolean built circuit          -> Boolgen(ctx, circuit).run(...) / .eval(...) / .eval_fields(...)
+                                                                (csrc/boolgen.hip); Builder.pack makes one field element of up to
+                                                                253 bit wires, so a digest is two public inputs instead of 256
 """
 import ctypes as C
 
@@ -47,8 +49,16 @@ class Circuit:
 
     @property
     def boolean(self):
-        """True where Boolgen takes the circuit: built, every input a bit wire, every sub-circuit from a boolean constructor."""
+        """True where Boolgen takes the circuit: built, every input a bit wire, every sub-circuit from a boolean constructor or a
+        pack over bit-valued wires whose output nothing reads."""
         return bool(self.lib.zk_circuit_is_boolean(self.ptr))
+
+    @property
+    def packed_wires(self):
+        """the number of packed wires (Builder.pack calls); 0 for parsed circuits"""
+        out = C.c_size_t()
+        self.lib.zk_circuit_packed_wires(self.ptr, C.byref(out))
+        return out.value
 
     def wire_index(self, wire):
         """witness index of a Builder wire id (built circuits only; the constant-zero wire has none)"""
@@ -273,6 +283,22 @@ class Builder:
         """the gate w (w - 1) = 0 without output wire: what forces an input to be 0 or 1 (not in the reference)"""
         self._check(self.lib.zk_builder_assert_bit(self.ptr, wire))
 
+    def pack(self, bits):
+        """-> the packed wire sum 2^i bits[i] of 1..253 wires, least significant first: one sub-circuit, a field element"""
+        a, ap = self._wires(bits)
+        out = C.c_uint32()
+        self._check(self.lib.zk_builder_pack(self.ptr, ap, a.size, C.byref(out)))
+        return out.value
+
+    def pack_bytes(self, wires, bytes_per_element=16):
+        """Word8s (or their wires, flat) -> a list of packed wires, bytes_per_element (at most 31) bytes each, little-endian per
+        element: a 32-byte digest is [int.from_bytes(d[:16], "little"), int.from_bytes(d[16:], "little")]"""
+        flat = self._flat(wires)
+        if bytes_per_element < 1 or len(flat) % 8:
+            raise BuildErr(_lib.ZK_ERR_ARG, "builder: pack_bytes takes whole bytes of 8 wires and at least one byte per element")
+        step = 8 * bytes_per_element
+        return [self.pack(flat[i:i + step]) for i in range(0, len(flat), step)]
+
     def fan_in(self, wires, gate):
         a, ap = self._wires(wires)
         out = C.c_uint32()
@@ -434,6 +460,13 @@ class Boolgen:
                                                  w.ctypes.data_as(_lib.u32p), w.size, C.c_void_p(d_out_ptr),
                                                  (w.size + 7) // 8 if out_stride is None else out_stride))
 
+    def eval_fields(self, d_in_ptr, count, wires, d_out_ptr, in_stride=None):
+        """the witness indices `wires`, bit and packed wires alike, as field elements: count x len(wires) x 4 canonical words -- with
+        wires = 1..l the `inputs` of Context.verify_batch"""
+        w = np.ascontiguousarray(np.asarray(list(wires), dtype=np.uint32))
+        self.ctx._check(self.lib.zk_boolgen_eval_fields(self.ptr, C.c_void_p(d_in_ptr), self.in_bytes if in_stride is None else in_stride, count,
+                                                        w.ctypes.data_as(_lib.u32p), w.size, C.c_void_p(d_out_ptr)))
+
     def _stage(self, in_bits):
         import torch
         a = np.ascontiguousarray(in_bits, dtype=np.uint8)
@@ -457,6 +490,15 @@ class Boolgen:
         torch.cuda.synchronize(dev)
         self.eval(d_in.data_ptr(), a.shape[0], wires, d_out.data_ptr(), in_stride=a.shape[1], out_stride=d_out.shape[1])
         return d_out.cpu().numpy()
+
+    def eval_fields_numpy(self, in_bits, wires):
+        """in_bits (count, stride) uint8 -> (count, len(wires), 4) uint64"""
+        torch, dev, a, d_in = self._stage(in_bits)
+        wires = list(wires)
+        d_out = torch.zeros((a.shape[0], len(wires), 4), dtype=torch.int64, device=dev)
+        torch.cuda.synchronize(dev)
+        self.eval_fields(d_in.data_ptr(), a.shape[0], wires, d_out.data_ptr(), in_stride=a.shape[1])
+        return d_out.cpu().numpy().view(np.uint64)
 
 
 class Witgen:

@@ -13,6 +13,11 @@
 //              exactly what zk_witgen_run writes.  Lane = wire: it loads its slot's word once and walks the 64 instances; a wave's
 //              stores cover 2 KiB contiguous of one instance's witness.
 //   pack       zk_boolgen_eval instead of expand (k_bool_pack): the named wires only, packed the way the inputs are.
+//   packed wires   (zk_builder_pack: out = sum 2^i b_i over at most 253 bit-valued operands) are no boolean operation and have no state:
+//              the value is below 2^253 < r, so its 4 canonical words ARE the operands' bits, gathered (pack_gather) -- no field
+//              arithmetic.  k_bool_expand_packs runs behind the expansion on the same stream and overwrites the 32 bytes the
+//              expansion wrote for a packed index from its never-written state slot, so no byte that is left depends on that slot;
+//              k_bool_pack_fields (zk_boolgen_eval_fields) returns named wires, bits and packed ones alike, as field elements.
 // Words run in chunks of as many as the scratch cap holds (option "boolgen_scratch_kib"); every word is independent of the others, so
 // the result does not depend on the chunking.  Mixed boolean / field circuits stay on the tape (zk_witgen_*).
 #include "pipeline.hpp"
@@ -26,6 +31,9 @@ struct zk_boolgen {
     bool expand_pair = false;
     zk::DevBuf<zk::BoolOp> ops;
     zk::DevBuf<uint32_t> level_ptr, in_wit, sel;
+    size_t n_packs = 0;
+    zk::DevBuf<uint32_t> pack_out, pack_ptr, pack_bits;      // Built's CSR lists
+    std::vector<std::pair<uint32_t, uint32_t>> pack_of;      // (witness index, pack) sorted by index: which named wires are packed
     zk::DevBuf<uint64_t> state;
 };
 
@@ -154,9 +162,67 @@ k_bool_pack(const uint64_t* __restrict__ state, size_t nw, size_t word0, size_t 
     }
 }
 
+// The 4 canonical words of a packed wire for instance `lane` of word w: bit i of the value is operand i's bit.  The operand index and
+// its state word do not depend on the lane (scalar loads); the four limbs are four named values, no indexed array.
+__device__ __forceinline__ uint64_t pack_limb(const uint64_t* __restrict__ state, size_t nw, size_t w, const uint32_t* __restrict__ bits,
+                                              unsigned lo, unsigned hi, unsigned lane) {
+    uint64_t v = 0;
+    for (unsigned e = lo; e < hi; ++e) v |= ((state[(size_t)bits[e] * nw + w] >> lane) & 1) << (e - lo);
+    return v;
+}
+__device__ __forceinline__ void pack_gather(const uint64_t* __restrict__ state, size_t nw, size_t w, const uint32_t* __restrict__ bits,
+                                            unsigned begin, unsigned end, unsigned lane, uint4& lo, uint4& hi) {
+    const uint64_t l0 = pack_limb(state, nw, w, bits, begin, min(end, begin + 64), lane);
+    const uint64_t l1 = pack_limb(state, nw, w, bits, min(end, begin + 64), min(end, begin + 128), lane);
+    const uint64_t l2 = pack_limb(state, nw, w, bits, min(end, begin + 128), min(end, begin + 192), lane);
+    const uint64_t l3 = pack_limb(state, nw, w, bits, min(end, begin + 192), end, lane);
+    lo = make_uint4((unsigned)l0, (unsigned)(l0 >> 32), (unsigned)l1, (unsigned)(l1 >> 32));
+    hi = make_uint4((unsigned)l2, (unsigned)(l2 >> 32), (unsigned)l3, (unsigned)(l3 >> 32));
+}
+
+// grid: (packs, words of the chunk); one wave, lane = instance.  Lanes behind `count` write nothing; there is no cross-lane operation.
+__global__ void __launch_bounds__(64)
+k_bool_expand_packs(const uint64_t* __restrict__ state, size_t nw, size_t word0, size_t count, unsigned m, const uint32_t* __restrict__ pack_out,
+                    const uint32_t* __restrict__ pack_ptr, const uint32_t* __restrict__ pack_bits, uint64_t* __restrict__ out) {
+    const unsigned p = blockIdx.x, lane = threadIdx.x;
+    const size_t w = blockIdx.y;
+    uint4 lo, hi;
+    pack_gather(state, nw, w, pack_bits, pack_ptr[p], pack_ptr[p + 1], lane, lo, hi);
+    const size_t j = (word0 + w) * 64 + lane;
+    if (j >= count) return;
+    uint4* o = reinterpret_cast<uint4*>(out + (j * m + pack_out[p]) * 4);
+    o[0] = lo;
+    o[1] = hi;
+}
+
+constexpr uint32_t BG_SEL_PACKED = 0x80000000u;   // sel entry: this bit | the pack's number, else a state slot (m < 2^31)
+
+// grid: (named wires, words of the chunk); one wave, lane = instance: out[(j * n_sel + i) * 4 ..] = wire sel[i] as 4 canonical words
+__global__ void __launch_bounds__(64)
+k_bool_pack_fields(const uint64_t* __restrict__ state, size_t nw, size_t word0, size_t count, const uint32_t* __restrict__ sel, unsigned n_sel,
+                   const uint32_t* __restrict__ pack_ptr, const uint32_t* __restrict__ pack_bits, uint64_t* __restrict__ out) {
+    const unsigned i = blockIdx.x, lane = threadIdx.x;
+    const size_t w = blockIdx.y;
+    const uint32_t s = sel[i];
+    uint4 lo, hi;
+    if (s & BG_SEL_PACKED) {
+        const unsigned p = s & ~BG_SEL_PACKED;
+        pack_gather(state, nw, w, pack_bits, pack_ptr[p], pack_ptr[p + 1], lane, lo, hi);
+    } else {
+        lo = make_uint4((unsigned)((state[(size_t)s * nw + w] >> lane) & 1), 0, 0, 0);
+        hi = make_uint4(0, 0, 0, 0);
+    }
+    const size_t j = (word0 + w) * 64 + lane;
+    if (j >= count) return;
+    uint4* o = reinterpret_cast<uint4*>(out + (j * n_sel + i) * 4);
+    o[0] = lo;
+    o[1] = hi;
+}
+
 static zk_boolgen* boolgen_create(zk_ctx* ctx, const zk_circuit& c) {
     ZK_REQUIRE(c.built && c.built->boolean, ZK_ERR_UNSUPPORTED,
-               "boolgen: the circuit is not boolean (a parsed program, a field input or a general sub-circuit); use zk_witgen_create");
+               "boolgen: the circuit is not boolean (a parsed program, a field input, a general sub-circuit or a packed wire that is read); "
+               "use zk_witgen_create");
     const Built& p = *c.built;
     const size_t m = c.u.size();
     ZK_REQUIRE(m < (1u << 31) && p.bool_ops.size() < (1u << 31), ZK_ERR_SIZE, "boolgen: circuit too large");
@@ -178,6 +244,13 @@ static zk_boolgen* boolgen_create(zk_ctx* ctx, const zk_circuit& c) {
     up(g->in_wit, p.in_wit);
     const std::vector<uint32_t> lp = p.bool_level_ptr.empty() ? std::vector<uint32_t>{0} : p.bool_level_ptr;
     up(g->level_ptr, lp);
+    g->n_packs = p.pack_out.size();
+    ZK_REQUIRE(g->n_packs < (1u << 31), ZK_ERR_SIZE, "boolgen: circuit too large");
+    up(g->pack_out, p.pack_out);
+    up(g->pack_ptr, p.pack_ptr);
+    up(g->pack_bits, p.pack_bits);
+    for (size_t k = 0; k < g->n_packs; ++k) g->pack_of.push_back({p.pack_out[k], (uint32_t)k});
+    std::sort(g->pack_of.begin(), g->pack_of.end());
     ZK_HIP(hipStreamSynchronize(st));   // the host vectors may go away with the circuit
     return g.release();
 }
@@ -221,13 +294,44 @@ static void boolgen_run(zk_boolgen& g, const void* d_in, size_t stride, size_t c
     zk_ctx* ctx = g.ctx;
     boolgen_chunks(g, d_in, stride, count, [&](size_t w0, size_t nw) {
         const size_t inst = std::min(count - w0 * 64, nw * 64);
-        ProfScope ps(ctx, "boolgen_expand", (double)inst * g.m * 32.0);
-        if (g.expand_pair)
-            hipLaunchKernelGGL(k_bool_expand_pair, dim3(ceil_div(2 * g.m, BG_EXPAND_THREADS), (unsigned)nw), dim3(BG_EXPAND_THREADS), 0, ctx->stream,
-                               g.state.p, nw, w0, count, (unsigned)g.m, (uint64_t*)d_out);
-        else
-            hipLaunchKernelGGL(k_bool_expand, dim3(ceil_div(g.m, BG_EXPAND_THREADS), (unsigned)nw), dim3(BG_EXPAND_THREADS), 0, ctx->stream, g.state.p, nw,
-                               w0, count, (unsigned)g.m, (uint64_t*)d_out);
+        {
+            ProfScope ps(ctx, "boolgen_expand", (double)inst * g.m * 32.0);
+            if (g.expand_pair)
+                hipLaunchKernelGGL(k_bool_expand_pair, dim3(ceil_div(2 * g.m, BG_EXPAND_THREADS), (unsigned)nw), dim3(BG_EXPAND_THREADS), 0, ctx->stream,
+                                   g.state.p, nw, w0, count, (unsigned)g.m, (uint64_t*)d_out);
+            else
+                hipLaunchKernelGGL(k_bool_expand, dim3(ceil_div(g.m, BG_EXPAND_THREADS), (unsigned)nw), dim3(BG_EXPAND_THREADS), 0, ctx->stream, g.state.p,
+                                   nw, w0, count, (unsigned)g.m, (uint64_t*)d_out);
+        }
+        if (g.n_packs) {   // behind the expansion on the same stream: the packed indices' 32 bytes are overwritten
+            ProfScope pp(ctx, "boolgen_expand_packs", (double)inst * g.n_packs * 32.0);
+            hipLaunchKernelGGL(k_bool_expand_packs, dim3((unsigned)g.n_packs, (unsigned)nw), dim3(64), 0, ctx->stream, g.state.p, nw, w0, count,
+                               (unsigned)g.m, g.pack_out.p, g.pack_ptr.p, g.pack_bits.p, (uint64_t*)d_out);
+        }
+    });
+}
+
+// the pack of witness index s, or -1
+static long boolgen_pack_of(const zk_boolgen& g, uint32_t s) {
+    auto it = std::lower_bound(g.pack_of.begin(), g.pack_of.end(), std::make_pair(s, (uint32_t)0));
+    return it != g.pack_of.end() && it->first == s ? (long)it->second : -1;
+}
+
+static void boolgen_eval_fields(zk_boolgen& g, const void* d_in, size_t stride, size_t count, const uint32_t* wires, size_t n_wires, void* d_out) {
+    zk_ctx* ctx = g.ctx;
+    std::vector<uint32_t> sel(n_wires);
+    for (size_t i = 0; i < n_wires; ++i) {
+        const long p = boolgen_pack_of(g, wires[i]);
+        sel[i] = p < 0 ? wires[i] : (BG_SEL_PACKED | (uint32_t)p);
+    }
+    g.sel.ensure(n_wires);
+    ZK_HIP(hipMemcpyAsync(g.sel.p, sel.data(), n_wires * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    ZK_HIP(hipStreamSynchronize(ctx->stream));   // sel is pageable host memory that goes away
+    boolgen_chunks(g, d_in, stride, count, [&](size_t w0, size_t nw) {
+        const size_t inst = std::min(count - w0 * 64, nw * 64);
+        ProfScope ps(ctx, "boolgen_pack_fields", (double)inst * n_wires * 32.0);
+        hipLaunchKernelGGL(k_bool_pack_fields, dim3((unsigned)n_wires, (unsigned)nw), dim3(64), 0, ctx->stream, g.state.p, nw, w0, count, g.sel.p,
+                           (unsigned)n_wires, g.pack_ptr.p, g.pack_bits.p, (uint64_t*)d_out);
     });
 }
 
@@ -279,9 +383,26 @@ int zk_boolgen_eval(zk_boolgen* g, const void* d_in_bits, size_t in_stride_bytes
         ZK_REQUIRE(n_wires < (1u << 31), ZK_ERR_ARG, "boolgen: too many wires named");
         for (size_t i = 0; i < n_wires; ++i)
             ZK_REQUIRE(wires[i] < g->m, ZK_ERR_ARG, "boolgen: witness index " + std::to_string(wires[i]) + " is not below m");
+        for (size_t i = 0; i < n_wires; ++i)
+            ZK_REQUIRE(boolgen_pack_of(*g, wires[i]) < 0, ZK_ERR_ARG,
+                       "boolgen: witness index " + std::to_string(wires[i]) + " is a packed wire, not a bit; use zk_boolgen_eval_fields");
         if (count == 0 || n_wires == 0) return;
         ZK_REQUIRE(d_out_bits && (d_in_bits || !g->n_in), ZK_ERR_ARG, "boolgen: null device pointer");
         boolgen_eval(*g, d_in_bits, in_stride_bytes, count, wires, n_wires, d_out_bits, out_stride_bytes);
+    });
+}
+int zk_boolgen_eval_fields(zk_boolgen* g, const void* d_in_bits, size_t in_stride_bytes, size_t count, const uint32_t* wires, size_t n_wires,
+                           void* d_out_words) {
+    if (!g) return ZK_ERR_ARG;
+    return guarded(g->ctx, [&] {
+        ZK_REQUIRE(in_stride_bytes >= (g->n_in + 7) / 8, ZK_ERR_ARG, "boolgen: in_stride_bytes is shorter than the packed inputs of one instance");
+        ZK_REQUIRE(wires || !n_wires, ZK_ERR_ARG, "boolgen: null wire list");
+        ZK_REQUIRE(n_wires < (1u << 31), ZK_ERR_ARG, "boolgen: too many wires named");
+        for (size_t i = 0; i < n_wires; ++i)
+            ZK_REQUIRE(wires[i] < g->m, ZK_ERR_ARG, "boolgen: witness index " + std::to_string(wires[i]) + " is not below m");
+        if (count == 0 || n_wires == 0) return;
+        ZK_REQUIRE(d_out_words && (d_in_bits || !g->n_in), ZK_ERR_ARG, "boolgen: null device pointer");
+        boolgen_eval_fields(*g, d_in_bits, in_stride_bytes, count, wires, n_wires, d_out_words);
     });
 }
 

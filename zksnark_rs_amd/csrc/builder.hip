@@ -103,6 +103,12 @@ int zk_builder_assert_bit(zk_builder* b, uint32_t wire) {
         o.assert_bit(wire);
     });
 }
+int zk_builder_pack(zk_builder* b, const uint32_t* bits, size_t n_bits, uint32_t* out) {
+    return builder_guard(b, [&](BuilderOps& o) {
+        if (!out || (n_bits && !bits)) BuilderOps::fail("null array");
+        *out = o.pack(bits, n_bits);
+    });
+}
 int zk_builder_finish(zk_builder* b, const uint32_t* verify_wires, size_t n_verify, zk_circuit** out) {
     if (!out) return ZK_ERR_ARG;
     *out = nullptr;

@@ -11,7 +11,7 @@
 // Every constructor emits exactly the reference's sub-circuits in the reference's order, so gate counts and weights are its own.
 // What differs, on purpose: wires are numbered and ordered deterministically (the reference iterates a HashMap); entries on the
 // constant-zero wire are dropped instead of becoming a witness wire that no constraint pins; its builder -> DummyRep conversion
-// (num_wires empty rows in front) is not reproduced; zk_builder_assert_bit exists.  Header-only and free of device code, so
+// (num_wires empty rows in front) is not reproduced; zk_builder_assert_bit and zk_builder_pack exist.  Header-only and free of device code, so
 // tests/cpp/builder_host.hip compiles it alone under the sanitizers.
 #pragma once
 #include <array>
@@ -21,7 +21,8 @@
 struct zk_builder {
     struct Term { zk::Fr w; uint32_t wire; };
     struct Sub { uint32_t l0, r0, end, out, bkind, a, b; };
-    std::vector<uint8_t> kind{0, 0};   // per wire id: 0 = a constant (ids 0 and 1), 1 = bit input, 2 = field input, 3 = a sub-circuit's output
+    // per wire id: 0 = a constant (ids 0 and 1), 1 = bit input, 2 = field input, 3 = a sub-circuit's output, 4 = a packed wire (zk_builder_pack)
+    std::vector<uint8_t> kind{0, 0};
     std::vector<Term> terms;
     std::vector<Sub> subs;
     bool boolean = true, finished = false;
@@ -52,6 +53,8 @@ struct BuilderOps {
     }
     uint32_t close_sub(uint32_t l0, uint32_t r0, bool with_out, uint32_t bkind, uint32_t x, uint32_t y) {
         if (b.subs.size() >= 0x7ffffff0u || b.terms.size() >= 0xfffffff0u) fail("too many sub-circuits");
+        for (size_t e = l0; e < b.terms.size(); ++e)      // a packed wire is a field element: whatever reads one is no boolean operation
+            if (b.kind[b.terms[e].wire] == 4) b.boolean = false;
         const uint32_t out = with_out ? new_wire(3) : WIT_NONE;
         b.subs.push_back({l0, r0, (uint32_t)b.terms.size(), out, bkind, x, y});
         return out;
@@ -78,6 +81,24 @@ struct BuilderOps {
         for (size_t i = 0; i < nr; ++i) b.terms.push_back({Fr::from_canonical(fr_from_words(rw + 4 * i)), rwire[i]});
         b.boolean = false;
         return close_sub(l0, r0, true, BOOL_NONE, 0, 0);
+    }
+    // (sum 2^i bits[i]) * (1) = out: a general sub-circuit whose output boolgen.hip gathers from the operands' bits, so the circuit stays
+    // boolean as long as the operands are bit-valued (a field input or a general sub-circuit has cleared the flag already, a packed
+    // operand clears it in close_sub)
+    uint32_t pack(const uint32_t* bits, size_t n) {
+        if (n < 1 || n > ZK_PACK_MAX_BITS) fail("pack: n_bits must be in 1.." + std::to_string(ZK_PACK_MAX_BITS) + ", got " + std::to_string(n));
+        for (size_t i = 0; i < n; ++i) known(bits[i]);
+        const uint32_t l0 = (uint32_t)b.terms.size();
+        for (size_t i = 0; i < n; ++i) {
+            uint64_t w[4] = {0, 0, 0, 0};
+            w[i / 64] = 1ull << (i % 64);
+            b.terms.push_back({Fr::from_canonical(fr_from_words(w)), bits[i]});
+        }
+        const uint32_t r0 = (uint32_t)b.terms.size();
+        b.terms.push_back({Fr::one(), 1});
+        const uint32_t out = close_sub(l0, r0, true, BOOL_PACK, 0, 0);
+        b.kind[out] = 4;
+        return out;
     }
 
     // ---- mod.rs:723-798, 939-950 ----
@@ -396,6 +417,11 @@ static zk_circuit* builder_finish(zk_builder& b, const uint32_t* verify, size_t 
         o.out = s.out == WIT_NONE ? WIT_NONE : wit[s.out];
         if (o.out != WIT_NONE) c->w[o.out].push_back({(uint32_t)k, one});
         p.subs.push_back(o);
+        if (s.bkind == BOOL_PACK) {
+            p.pack_out.push_back(o.out);
+            for (uint32_t e = s.l0; e < s.r0; ++e) p.pack_bits.push_back(wit[b.terms[e].wire] == WIT_NONE ? (uint32_t)m : wit[b.terms[e].wire]);
+            p.pack_ptr.push_back((uint32_t)p.pack_bits.size());
+        }
     }
     p.boolean = b.boolean;
     p.wire_wit = wit;
@@ -411,7 +437,7 @@ static zk_circuit* builder_finish(zk_builder& b, const uint32_t* verify, size_t 
         auto idx = [&](uint32_t wire) { return wit[wire] == WIT_NONE ? (uint32_t)m : wit[wire]; };
         std::vector<uint32_t> level(m + 1, 0), op_level;
         for (const zk_builder::Sub& s : b.subs) {
-            if (s.out == WIT_NONE) continue;
+            if (s.out == WIT_NONE || s.bkind == BOOL_PACK) continue;   // an assertion computes nothing; a pack is no boolean operation
             const BoolOp op{wit[s.out], idx(s.a), idx(s.b), s.bkind};
             const uint32_t lv = 1 + std::max(level[op.a], level[op.b]);
             level[op.dst] = lv;

@@ -33,7 +33,8 @@ struct BuiltSub {    // (sum of terms[l0, r0)) * (sum of terms[r0, end)) = witne
 };
 // one boolean operation per sub-circuit of a boolean circuit: dst, a, b are witness indices; index m is the constant 0, index 0 the
 // constant 1.  LESS = !a & b, GREATER = a & !b (builder/mod.rs:939-950); ZERO is the bit checker's output x (x - 1).
-enum BoolKind : uint32_t { BOOL_ZERO = 0, BOOL_NOT, BOOL_AND, BOOL_OR, BOOL_XOR, BOOL_NOR, BOOL_XNOR, BOOL_LESS, BOOL_GREATER, BOOL_NONE };
+// NONE marks a sub-circuit that is no boolean operation, PACK the one of zk_builder_pack: its output is a field element, not a bit.
+enum BoolKind : uint32_t { BOOL_ZERO = 0, BOOL_NOT, BOOL_AND, BOOL_OR, BOOL_XOR, BOOL_NOR, BOOL_XNOR, BOOL_LESS, BOOL_GREATER, BOOL_NONE, BOOL_PACK };
 struct BoolOp {
     uint32_t dst, a, b, kind;
 };
@@ -46,6 +47,10 @@ struct Built {
     bool boolean = false;
     std::vector<BoolOp> bool_ops;          // sorted by level (stable), as the field tape
     std::vector<uint32_t> bool_level_ptr;  // levels + 1 entries
+    // zk_builder_pack, in CSR form: pack p has output witness index pack_out[p] and operands pack_bits[pack_ptr[p] .. pack_ptr[p + 1]),
+    // witness indices in bit order (position in the list = bit position; index m is the constant 0 and keeps its place, index 0 the
+    // constant 1).  Kept whether the circuit is boolean or not.
+    std::vector<uint32_t> pack_out, pack_ptr{0}, pack_bits;
 };
 
 static inline std::string bit_input_error(size_t instance, size_t input, uint32_t wire) {

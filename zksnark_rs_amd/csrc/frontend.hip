@@ -683,6 +683,11 @@ int zk_circuit_qap_sparse_unity(zk_ctx* ctx, const zk_circuit* c, zk_qap** out) 
     return guarded(ctx, [&] { *out = circuit_to_qap_sparse(ctx, *c, true); });
 }
 int zk_circuit_is_boolean(const zk_circuit* c) { return c && c->built && c->built->boolean ? 1 : 0; }
+int zk_circuit_packed_wires(const zk_circuit* c, size_t* count) {
+    if (!c || !count) return ZK_ERR_ARG;
+    *count = c->built ? c->built->pack_out.size() : 0;
+    return ZK_OK;
+}
 int zk_circuit_wire_index(const zk_circuit* c, uint32_t wire, size_t* index) {
     if (!c || !index || !c->built || wire >= c->built->wire_wit.size() || c->built->wire_wit[wire] == WIT_NONE) return ZK_ERR_ARG;
     *index = c->built->wire_wit[wire];
