@@ -197,6 +197,16 @@ extern "C" {
     fn zk_circuit_packed_wires(c: *const ZkCircuit, count: *mut usize) -> c_int;
     fn zk_circuit_wire_index(c: *const ZkCircuit, wire: u32, index: *mut usize) -> c_int;
     fn zk_circuit_qap_sparse_unity(ctx: *mut ZkCtx, c: *const ZkCircuit, out: *mut *mut ZkQap) -> c_int;
+    fn zk_circuit_mixed_dims(c: *const ZkCircuit, n_bit_inputs: *mut usize, n_field_inputs: *mut usize, core_ops: *mut usize, core_levels: *mut usize,
+                             tail_ops: *mut usize, tail_levels: *mut usize, tail_slots: *mut usize) -> c_int;
+    fn zk_circuit_weights_mixed(c: *const ZkCircuit, in_bits: *const u8, n_bit_bytes: usize, in_fields: *const u64, n_field: usize,
+                                weights_out: *mut u64, m: usize) -> c_int;
+    fn zk_mixgen_create(ctx: *mut ZkCtx, c: *const ZkCircuit, out: *mut *mut ZkMixgen) -> c_int;
+    fn zk_mixgen_free(g: *mut ZkMixgen);
+    fn zk_mixgen_run(g: *mut ZkMixgen, d_in_bits: *const c_void, in_stride_bytes: usize, d_in_fields: *const c_void, count: usize,
+                     d_weights_out: *mut c_void, m: usize) -> c_int;
+    fn zk_mixgen_eval_fields(g: *mut ZkMixgen, d_in_bits: *const c_void, in_stride_bytes: usize, d_in_fields: *const c_void, count: usize,
+                             wires: *const u32, n_wires: usize, d_out_words: *mut c_void) -> c_int;
     fn zk_boolgen_create(ctx: *mut ZkCtx, c: *const ZkCircuit, out: *mut *mut ZkBoolgen) -> c_int;
     fn zk_boolgen_free(g: *mut ZkBoolgen);
     fn zk_boolgen_run(g: *mut ZkBoolgen, d_in_bits: *const c_void, in_stride_bytes: usize, count: usize, d_weights_out: *mut c_void,
@@ -261,6 +271,7 @@ extern "C" {
 #[repr(C)] pub struct ZkWitgen { _p: [u8; 0] }
 #[repr(C)] pub struct ZkBuilder { _p: [u8; 0] }
 #[repr(C)] pub struct ZkBoolgen { _p: [u8; 0] }
+#[repr(C)] pub struct ZkMixgen { _p: [u8; 0] }
 #[repr(C)] pub struct ZkMgpu { _p: [u8; 0] }
 
 fn check(ctx: *mut ZkCtx, rc: c_int) {
@@ -1337,6 +1348,26 @@ impl BuiltCircuit {
         unsafe { zk_circuit_dims(self.0, &mut m, &mut n, &mut l, &mut k) };
         (m, n, l, k)
     }
+    /// the split into a boolean core and a field tail (zk_circuit_mixed_dims)
+    pub fn mixed_dims(&self) -> MixedDims {
+        let mut d = MixedDims::default();
+        unsafe {
+            zk_circuit_mixed_dims(self.0, &mut d.n_bit_inputs, &mut d.n_field_inputs, &mut d.core_ops, &mut d.core_levels, &mut d.tail_ops,
+                                  &mut d.tail_levels, &mut d.tail_slots)
+        };
+        d
+    }
+    /// one witness through the split on the host (zk_circuit_weights_mixed): packed bit inputs, field inputs of 4 canonical words each
+    /// -> m x 4 words, or the status (ZK_ERR_RANGE for a field input >= r)
+    pub fn weights_mixed(&self, in_bits: &[u8], in_fields: &[[u64; 4]]) -> Result<Vec<[u64; 4]>, c_int> {
+        let m = self.dims().0;
+        let mut out = vec![[0u64; 4]; m];
+        let rc = unsafe {
+            zk_circuit_weights_mixed(self.0, in_bits.as_ptr(), in_bits.len(), in_fields.as_ptr() as *const u64, in_fields.len(),
+                                     out.as_mut_ptr() as *mut u64, m)
+        };
+        if rc == 0 { Ok(out) } else { Err(rc) }
+    }
     /// the rows at the roots of unity (zk_circuit_qap_sparse_unity); free with zk_qap_free
     pub fn qap_sparse_unity(&self, ctx: *mut ZkCtx) -> *mut ZkQap {
         let mut q: *mut ZkQap = std::ptr::null_mut();
@@ -1364,6 +1395,35 @@ impl Boolgen {
     /// bit and packed wires alike as 4 canonical words each: with wires = 1..l the `inputs` of zk_verify_batch
     pub fn eval_fields(&self, d_in_bits: *const c_void, in_stride_bytes: usize, count: usize, wires: &[u32], d_out_words: *mut c_void) {
         unsafe { check(self.ctx, zk_boolgen_eval_fields(self.g, d_in_bits, in_stride_bytes, count, wires.as_ptr(), wires.len(), d_out_words)) }
+    }
+}
+
+/// what zk_circuit_mixed_dims reports
+#[derive(Default, Debug, Clone, Copy, PartialEq, Eq)]
+pub struct MixedDims {
+    pub n_bit_inputs: usize, pub n_field_inputs: usize, pub core_ops: usize, pub core_levels: usize,
+    pub tail_ops: usize, pub tail_levels: usize, pub tail_slots: usize,
+}
+
+/// zk_mixgen_*: witnesses of ANY built circuit -- the boolean core bit-sliced, the field tail one instance per lane -- for `count`
+/// input sets (packed bit rows and field inputs of 4 canonical words each), left in device memory in zk_witgen_run's layout
+pub struct Mixgen { ctx: *mut ZkCtx, g: *mut ZkMixgen, m: usize }
+impl Drop for Mixgen { fn drop(&mut self) { unsafe { zk_mixgen_free(self.g) } } }
+impl Mixgen {
+    pub fn new(ctx: *mut ZkCtx, circuit: &BuiltCircuit) -> Self {
+        let mut g: *mut ZkMixgen = std::ptr::null_mut();
+        unsafe { check(ctx, zk_mixgen_create(ctx, circuit.0, &mut g)) };
+        Mixgen { ctx, g, m: circuit.dims().0 }
+    }
+    pub fn run(&self, d_in_bits: *const c_void, in_stride_bytes: usize, d_in_fields: *const c_void, count: usize, d_weights_out: *mut c_void) {
+        unsafe { check(self.ctx, zk_mixgen_run(self.g, d_in_bits, in_stride_bytes, d_in_fields, count, d_weights_out, self.m)) }
+    }
+    /// wires of either class as 4 canonical words each: with wires = 1..l the `inputs` of zk_verify_batch
+    pub fn eval_fields(&self, d_in_bits: *const c_void, in_stride_bytes: usize, d_in_fields: *const c_void, count: usize, wires: &[u32],
+                       d_out_words: *mut c_void) {
+        unsafe {
+            check(self.ctx, zk_mixgen_eval_fields(self.g, d_in_bits, in_stride_bytes, d_in_fields, count, wires.as_ptr(), wires.len(), d_out_words))
+        }
     }
 }
 

@@ -448,6 +448,52 @@ int zk_boolgen_eval(zk_boolgen* g, const void* d_in_bits, size_t in_stride_bytes
 int zk_boolgen_eval_fields(zk_boolgen* g, const void* d_in_bits, size_t in_stride_bytes, size_t count, const uint32_t* wires,
                            size_t n_wires, void* d_out_words);
 
+/* Mixed circuits on the bit-sliced path (csrc/mixgen.hip).  zk_builder_finish splits EVERY built circuit into a boolean core and a
+ * field tail.  A witness index is bit-class if it is the constant 1, a ZK_WIRE_BIT input or the output of a gate (bit checker .. greater
+ * than, the sub-circuits of comparators and the sponge included) whose operands are bit-class; every other index is field-class: a
+ * ZK_WIRE_FIELD input, the output of zk_builder_sub_circuit, a packed wire, and whatever reads one of these.  Nothing bit-class reads
+ * anything field-class.  The core is one boolean operation per bit-class sub-circuit (for a boolean circuit: the tape of
+ * zk_boolgen_*); a pack whose operands are all bit-class is gathered from their bits; every other sub-circuit with an output is a
+ * tail operation, compiled from its weights like the tape of zk_witgen_* (an XOR gate on a field wire is (x - y)(x - y)).
+ * *n_bit_inputs / *n_field_inputs: the ZK_WIRE_BIT / ZK_WIRE_FIELD inputs; *core_ops, *core_levels: the boolean tape;
+ * *tail_ops, *tail_levels: the field tape (a core pack that the tail reads costs one copy); *tail_slots: field elements the tail
+ * keeps per instance (field inputs, field-class wires it computes, temporaries).  Any pointer may be NULL.  A parsed circuit:
+ * ZK_ERR_UNSUPPORTED with text.  zk_builder_finish answers ZK_ERR_SIZE for a circuit with 2^30 or more witness indices, packs, tail
+ * slots, tail operations or constants: a tail operand keeps two bits of its 32 to say what it names. */
+int zk_circuit_mixed_dims(const zk_circuit* c, size_t* n_bit_inputs, size_t* n_field_inputs, size_t* core_ops, size_t* core_levels,
+                          size_t* tail_ops, size_t* tail_levels, size_t* tail_slots);
+/* One witness through the split on the host: what the kernels of zk_mixgen_run compute for one instance, the way
+ * zk_circuit_weights_tape is zk_witgen_run's model.  in_bits: the ZK_WIRE_BIT inputs packed, bit k % 8 of byte k / 8 = the k-th such
+ * input in input order, n_bit_bytes = ceil(n_bit_inputs / 8) (bits past the last input are ignored); in_fields: the ZK_WIRE_FIELD
+ * inputs in input order, 4 canonical words each.  weights_out: m x 4 words, those of zk_circuit_weights on the same values.  Status and
+ * text as zk_circuit_weights: a wrong n_bit_bytes, n_field or m is ZK_ERR_ARG "StructureErr(...)", a field input >= r ZK_ERR_RANGE;
+ * a parsed circuit is ZK_ERR_UNSUPPORTED. */
+int zk_circuit_weights_mixed(const zk_circuit* c, const uint8_t* in_bits, size_t n_bit_bytes, const uint64_t* in_fields, size_t n_field,
+                             uint64_t* weights_out, size_t m);
+typedef struct zk_mixgen zk_mixgen;
+/* uploads the core tape, the core packs, the tail tape with its constants and the tail's slot -> witness index table; the circuit
+ * may be freed afterwards, the context must outlive the generator.  Takes any built circuit, boolean ones included (the tail is then
+ * empty and zk_mixgen_run writes the bytes of zk_boolgen_run); a parsed circuit -> ZK_ERR_UNSUPPORTED with text.  Options, read here:
+ * "boolgen_group_words" and "boolgen_expand_form" as for zk_boolgen_create; "boolgen_scratch_kib" caps state plus tail scratch, and a
+ * word of 64 instances needs (m + 1) x 8 + tail_slots x 64 x 32 bytes: a circuit of which one word does not fit gives ZK_ERR_SIZE
+ * naming the option. */
+int zk_mixgen_create(zk_ctx* ctx, const zk_circuit* c, zk_mixgen** out);
+void zk_mixgen_free(zk_mixgen* g);       /* NULL is a no-op */
+/* The witnesses of `count` input sets.  d_in_bits: the ZK_WIRE_BIT inputs, packed as for zk_boolgen_run (bit k = the k-th such input
+ * in input order) at d_in_bits + j * in_stride_bytes; d_in_fields: the ZK_WIRE_FIELD inputs, 4 canonical words each, n_field_inputs
+ * per instance, instance-major (may be NULL where the circuit has none).  d_weights_out: exactly zk_witgen_run's, count x m x 4 words,
+ * canonical, instance-major: zk_prove_batch_submit and zk_qap_check_dev take it unchanged.  All device pointers.  Complete on return.
+ * count == 0: ZK_OK, nothing touched.  m not the circuit's or in_stride_bytes < ceil(n_bit_inputs / 8): ZK_ERR_ARG.  A field input
+ * whose word pattern is >= r: ZK_ERR_RANGE with text naming the LOWEST such instance, as zk_witgen_run; the output is then
+ * unspecified.  The instances run in chunks under the scratch cap and the result does not depend on the chunking. */
+int zk_mixgen_run(zk_mixgen* g, const void* d_in_bits, size_t in_stride_bytes, const void* d_in_fields, size_t count, void* d_weights_out,
+                  size_t m);
+/* wires[i] (witness indices < m of either class: bits, packed wires, tail wires, field inputs) of instance j -> 4 canonical words at
+ * d_out_words + (j * n_wires + i) * 4, the layout of zk_boolgen_eval_fields: with wires = 1..l the `inputs` array of zk_verify_batch.
+ * Nothing is expanded and nothing else is written.  Errors as zk_mixgen_run; an index >= m: ZK_ERR_ARG. */
+int zk_mixgen_eval_fields(zk_mixgen* g, const void* d_in_bits, size_t in_stride_bytes, const void* d_in_fields, size_t count,
+                          const uint32_t* wires, size_t n_wires, void* d_out_words);
+
 /* ------------------------------------------------------------------------------------------
  * CRS  (SigmaG1 / SigmaG2, groth16/mod.rs:105-121)
  * ---------------------------------------------------------------------------------------- */

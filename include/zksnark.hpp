@@ -125,6 +125,23 @@ class Circuit {
         if (zk_circuit_wire_index(c_, wire, &i) != ZK_OK) throw Error(ZK_ERR_ARG, "wire_index: the wire has no witness index in this circuit");
         return i;
     }
+    // the split of a built circuit into a boolean core and a field tail (zk_circuit_mixed_dims)
+    struct MixedDims { size_t n_bit_inputs, n_field_inputs, core_ops, core_levels, tail_ops, tail_levels, tail_slots; };
+    MixedDims mixed_dims() const {
+        MixedDims d{};
+        int rc = zk_circuit_mixed_dims(c_, &d.n_bit_inputs, &d.n_field_inputs, &d.core_ops, &d.core_levels, &d.tail_ops, &d.tail_levels, &d.tail_slots);
+        if (rc != ZK_OK) throw Error(rc, std::string("mixed_dims: ") + zk_circuit_last_error(c_));
+        return d;
+    }
+    // weights() through the split, the host model of Mixgen::run: the bit inputs packed (bit k % 8 of byte k / 8 = the k-th bit input),
+    // the field inputs in input order
+    std::vector<FrLocal> weights_mixed(const std::vector<uint8_t>& in_bits, const std::vector<FrLocal>& in_fields) const {
+        std::vector<FrLocal> out(wires());
+        int rc = zk_circuit_weights_mixed(c_, in_bits.empty() ? nullptr : in_bits.data(), in_bits.size(),
+                                          in_fields.empty() ? nullptr : in_fields[0].w.data(), in_fields.size(), out[0].w.data(), out.size());
+        if (rc != ZK_OK) throw Error(rc, std::string("weights_mixed: ") + zk_circuit_last_error(c_));
+        return out;
+    }
     size_t wires() const { return dims()[0]; }
     size_t gates() const { return dims()[1]; }
     size_t input() const { return dims()[2]; }
@@ -410,6 +427,28 @@ class Boolgen {
    private:
     const Context& c_;
     zk_boolgen* g_ = nullptr;
+};
+
+// zk_mixgen_*: the witnesses of ANY built circuit for many input sets at once: the boolean core bit-sliced, the field tail one instance
+// per lane (device pointers in and out; d_in_fields: 4 canonical words per field input, instance-major)
+class Mixgen {
+   public:
+    Mixgen(const Context& c, const Circuit& circuit) : c_(c) { c.check(zk_mixgen_create(c.get(), circuit.get(), &g_), "Mixgen"); }
+    Mixgen(const Mixgen&) = delete;
+    ~Mixgen() { zk_mixgen_free(g_); }
+    void run(const void* d_in_bits, size_t in_stride_bytes, const void* d_in_fields, size_t count, void* d_weights_out, size_t m) const {
+        c_.check(zk_mixgen_run(g_, d_in_bits, in_stride_bytes, d_in_fields, count, d_weights_out, m), "Mixgen::run");
+    }
+    // wires of either class as 4 canonical words each: with wires = 1..l the `inputs` of zk_verify_batch
+    void eval_fields(const void* d_in_bits, size_t in_stride_bytes, const void* d_in_fields, size_t count, const std::vector<uint32_t>& wires,
+                     void* d_out_words) const {
+        c_.check(zk_mixgen_eval_fields(g_, d_in_bits, in_stride_bytes, d_in_fields, count, wires.data(), wires.size(), d_out_words),
+                 "Mixgen::eval_fields");
+    }
+
+   private:
+    const Context& c_;
+    zk_mixgen* g_ = nullptr;
 };
 
 namespace groth16 {

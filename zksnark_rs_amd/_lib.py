@@ -187,6 +187,12 @@ SIGNATURES = {
     "zk_boolgen_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t]),
     "zk_boolgen_eval": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, u32p, C.c_size_t, C.c_void_p, C.c_size_t]),
     "zk_boolgen_eval_fields": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, u32p, C.c_size_t, C.c_void_p]),
+    "zk_circuit_mixed_dims": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_size_t)] * 7),
+    "zk_circuit_weights_mixed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, u64p, C.c_size_t, u64p, C.c_size_t]),
+    "zk_mixgen_create": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "zk_mixgen_free": (None, [C.c_void_p]),
+    "zk_mixgen_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
+    "zk_mixgen_eval_fields": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, u32p, C.c_size_t, C.c_void_p]),
     "zk_msm_auto_window": (C.c_int, [C.c_size_t]),
     "zk_msm_auto_window_g2": (C.c_int, [C.c_size_t]),
     "zk_circuit_qap": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),

@@ -8,6 +8,9 @@
 and its gate-level circuit builder (circuit/builder/mod.rs, types.rs; host code as well):
 
     Circuit<T>, new_word8 .. keccak256, validate_order       -> Builder, whose finish() is an ordinary Circuit
+    bit-sliced witnesses of any built circuit                -> Mixgen(ctx, circuit).run(...) / .eval_fields(...) (csrc/mixgen.hip):
+                                                                the boolean core bit-sliced, the field tail one instance per lane;
+                                                                Circuit.mixed_dims / .weights_mixed are the split and its host model
     bit-sliced witnesses of a boolean built circuit          -> Boolgen(ctx, circuit).run(...) / .eval(...) / .eval_fields(...)
                                                                 (csrc/boolgen.hip); Builder.pack makes one field element of up to
                                                                 253 bit wires, so a digest is two public inputs instead of 256
@@ -114,6 +117,30 @@ class Circuit:
         if rc != 0:
             raise ParseErr(self.lib.zk_circuit_last_error(self.ptr).decode())
         return dict(zip(("ops", "slots", "consts", "depth", "width"), (x.value for x in v)))
+
+    def mixed_dims(self):
+        """the split of a built circuit into a boolean core and a field tail (zk_circuit_mixed_dims): dict(n_bit_inputs,
+        n_field_inputs, core_ops, core_levels, tail_ops, tail_levels, tail_slots)"""
+        v = [C.c_size_t() for _ in range(7)]
+        rc = self.lib.zk_circuit_mixed_dims(self.ptr, *[C.byref(x) for x in v])
+        if rc != 0:
+            raise ParseErr(self.lib.zk_circuit_last_error(self.ptr).decode())
+        return dict(zip(("n_bit_inputs", "n_field_inputs", "core_ops", "core_levels", "tail_ops", "tail_levels", "tail_slots"), (x.value for x in v)))
+
+    def weights_mixed(self, in_bits, in_fields=()):
+        """weights() through the split, the host model of Mixgen.run: in_bits the bit inputs packed (bytes or uint8 array, bit k % 8 of
+        byte k / 8 = the k-th bit input), in_fields the field inputs in input order (ints or (n, 4) limbs) -> (m, 4) witness"""
+        bits = np.ascontiguousarray(np.frombuffer(bytes(in_bits), np.uint8) if not isinstance(in_bits, np.ndarray) else in_bits, dtype=np.uint8)
+        if isinstance(in_fields, np.ndarray):
+            f = np.ascontiguousarray(in_fields, dtype=np.uint64).reshape(-1, 4)
+        else:
+            f = ints_to_limbs(list(in_fields)) if len(in_fields) else np.zeros((0, 4), np.uint64)
+        out = np.zeros((self.m, 4), np.uint64)
+        rc = self.lib.zk_circuit_weights_mixed(self.ptr, bits.ctypes.data_as(C.c_void_p), bits.size, f.ctypes.data_as(_lib.u64p), f.shape[0],
+                                               out.ctypes.data_as(_lib.u64p), self.m)
+        if rc != 0:
+            raise ParseErr(self.lib.zk_circuit_last_error(self.ptr).decode())
+        return out
 
     def qap(self, ctx):
         p = C.c_void_p()
@@ -498,6 +525,93 @@ class Boolgen:
         d_out = torch.zeros((a.shape[0], len(wires), 4), dtype=torch.int64, device=dev)
         torch.cuda.synchronize(dev)
         self.eval_fields(d_in.data_ptr(), a.shape[0], wires, d_out.data_ptr(), in_stride=a.shape[1])
+        return d_out.cpu().numpy().view(np.uint64)
+
+
+class Mixgen:
+    """zk_mixgen_*: the witnesses of any built circuit for many input sets at once: the boolean core bit-sliced as Boolgen runs it, the
+    field tail as a small field tape with one instance per lane (csrc/mixgen.hip).  Bit inputs are packed as for Boolgen (bit k = the
+    k-th bit input in input order), field inputs are 4 canonical words each, n_field per instance.  scratch_kib / group_words /
+    expand_form: the options "boolgen_scratch_kib" (here the cap of state plus tail scratch), "boolgen_group_words" and
+    "boolgen_expand_form" for this generator (None = the context's)."""
+
+    def __init__(self, ctx, circuit, scratch_kib=None, group_words=None, expand_form=None):
+        self.ctx, self.lib = ctx, ctx.lib
+        dims = circuit.mixed_dims()
+        self.n_bit, self.n_field, self.m = dims["n_bit_inputs"], dims["n_field_inputs"], circuit.m
+        self.in_bytes = (self.n_bit + 7) // 8
+        p = C.c_void_p()
+        keep = {}
+        for key, val in (("boolgen_scratch_kib", scratch_kib), ("boolgen_group_words", group_words), ("boolgen_expand_form", expand_form)):
+            if val is not None:
+                keep[key] = ctx.get_option(key)
+                ctx.set_option(key, val)
+        try:
+            rc = self.lib.zk_mixgen_create(ctx.ptr, circuit.ptr, C.byref(p))
+        finally:
+            for key, val in keep.items():
+                ctx.set_option(key, val)
+        ctx._check(rc)
+        self.ptr = p
+
+    def close(self):
+        if getattr(self, "ptr", None):
+            self.lib.zk_mixgen_free(self.ptr)
+            self.ptr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def run(self, d_in_ptr, d_fields_ptr, count, d_out_ptr, in_stride=None, m=None):
+        """d_in_ptr: count rows of in_stride bytes (default ceil(n_bit / 8)); d_fields_ptr: count x n_field x 4 words (None or 0 where
+        the circuit has no field input); d_out_ptr: count x m x 4 words, as Witgen.run writes"""
+        self.ctx._check(self.lib.zk_mixgen_run(self.ptr, C.c_void_p(d_in_ptr), self.in_bytes if in_stride is None else in_stride,
+                                               C.c_void_p(d_fields_ptr), count, C.c_void_p(d_out_ptr), self.m if m is None else m))
+
+    def run_checked(self, qap, d_in_ptr, d_fields_ptr, count, d_out_ptr, in_stride=None):
+        """run(), then zk_qap_check_dev on the witnesses where they lie, as Witgen.run_checked"""
+        self.run(d_in_ptr, d_fields_ptr, count, d_out_ptr, in_stride=in_stride)
+        return self.ctx.qap_check_dev(qap, d_out_ptr, self.m, count)
+
+    def eval_fields(self, d_in_ptr, d_fields_ptr, count, wires, d_out_ptr, in_stride=None):
+        """the witness indices `wires` of either class as field elements: count x len(wires) x 4 canonical words -- with wires = 1..l
+        the `inputs` of Context.verify_batch.  Nothing is expanded."""
+        w = np.ascontiguousarray(np.asarray(list(wires), dtype=np.uint32))
+        self.ctx._check(self.lib.zk_mixgen_eval_fields(self.ptr, C.c_void_p(d_in_ptr), self.in_bytes if in_stride is None else in_stride,
+                                                       C.c_void_p(d_fields_ptr), count, w.ctypes.data_as(_lib.u32p), w.size, C.c_void_p(d_out_ptr)))
+
+    def _stage(self, in_bits, in_fields):
+        import torch
+        a = np.ascontiguousarray(in_bits, dtype=np.uint8)
+        a = a.reshape(-1, a.shape[-1]) if a.ndim > 1 else a.reshape(-1, max(self.in_bytes, 1))
+        dev = "cuda:%d" % self.ctx.device
+        d_f = None
+        if self.n_field:
+            f = np.ascontiguousarray(in_fields, dtype=np.uint64).reshape(a.shape[0], self.n_field, 4)
+            d_f = torch.from_numpy(f.view(np.int64)).to(dev)
+        return torch, dev, a, torch.from_numpy(a).to(dev), d_f
+
+    def run_numpy(self, in_bits, in_fields=(), fill=None):
+        """in_bits (count, stride) uint8, in_fields (count, n_field, 4) uint64 -> (count, m, 4) uint64, staged through torch tensors on
+        the context's device; fill: a byte the output buffer holds before the call"""
+        torch, dev, a, d_in, d_f = self._stage(in_bits, in_fields)
+        d_out = torch.empty((a.shape[0], self.m, 4), dtype=torch.int64, device=dev)
+        if fill is not None:
+            d_out.view(torch.uint8).fill_(fill)
+        torch.cuda.synchronize(dev)
+        self.run(d_in.data_ptr(), d_f.data_ptr() if d_f is not None else None, a.shape[0], d_out.data_ptr(), in_stride=a.shape[1])
+        return d_out.cpu().numpy().view(np.uint64)
+
+    def eval_fields_numpy(self, in_bits, in_fields, wires):
+        """-> (count, len(wires), 4) uint64"""
+        torch, dev, a, d_in, d_f = self._stage(in_bits, in_fields)
+        wires = list(wires)
+        d_out = torch.zeros((a.shape[0], len(wires), 4), dtype=torch.int64, device=dev)
+        torch.cuda.synchronize(dev)
+        self.eval_fields(d_in.data_ptr(), d_f.data_ptr() if d_f is not None else None, a.shape[0], wires, d_out.data_ptr(), in_stride=a.shape[1])
         return d_out.cpu().numpy().view(np.uint64)
 
 

@@ -1,5 +1,6 @@
 // builder.hpp -- the reference's gate-level circuit builder (host code, as in the reference) and what a finished circuit needs to be an
-// ordinary zk_circuit: rows, the two host evaluators' program, the field tape of witgen.hip and the boolean tape of boolgen.hip.
+// ordinary zk_circuit: rows, the two host evaluators' program, the field tape of witgen.hip, the boolean tape of boolgen.hip, and the
+// split into a boolean core and a field tail that mixgen.hip runs (built_split), with its host runner (mixed_run_host).
 //
 //   Circuit::new, zero / unity wire, new_wire        circuit/builder/mod.rs:91-125
 //   new_sub_circuit                                  mod.rs:491-557 (weights and wires of (sum left) * (sum right) = out)
@@ -292,19 +293,14 @@ static std::vector<uint32_t> sort_by_level(std::vector<Op>& ops, const std::vect
     return ptr;
 }
 
-// The sub-circuits as a zk::Tape (witgen_tape.hpp): a scaled sum is MUL by a pooled constant and ADD into fresh temporaries, a weight
-// of one reads the slot itself, an entry on the constant 1 is the pooled weight, and a side that repeats the other (XOR) is summed once.
-static void built_compile_tape(zk_circuit& c) {
-    const Built& p = *c.built;
-    Tape& t = c.tape;
-    const size_t m = c.u.size();
-    t.n_in = p.in_wit.size();
-    t.m = m;
-    t.slots = m;
-    t.in_slot = p.in_wit;
-    t.in_bit.resize(t.n_in);
-    for (size_t i = 0; i < t.n_in; ++i) t.in_bit[i] = p.in_bit[i] ? p.in_wire[i] + 1 : 0;
-    std::vector<uint32_t> slot_level(m, 0), node_level(m, 0), op_level, per_level;
+// Sub-circuits as operations of a zk::Tape (witgen_tape.hpp): a scaled sum is MUL by a pooled constant and ADD into fresh temporaries,
+// a weight of one reads the operand itself, an entry on the constant 1 is the pooled weight, and a side that repeats the other (XOR)
+// is summed once.  `take(k)` says whether sub-circuit k is compiled, `ref(i, copy)` is the operand word of witness index i > 0 (for
+// an output, its slot), where copy(x) emits a COPY of operand word x into a fresh temporary and returns that slot; `tags` are the bits
+// that mark an operand word as no slot.  Returns the level of every operation, in order.
+template <class Take, class Ref>
+static std::vector<uint32_t> built_compile_subs(const Built& p, Tape& t, uint32_t tags, Take&& take, Ref&& ref) {
+    std::vector<uint32_t> slot_level(t.slots, 0), op_level;
     std::map<std::array<uint32_t, 8>, uint32_t> pool;
     auto constant = [&](const Fr& v) {
         std::array<uint32_t, 8> key;
@@ -314,7 +310,7 @@ static void built_compile_tape(zk_circuit& c) {
         return it->second | TAPE_CONST;
     };
     auto fresh = [&]() { slot_level.push_back(0); return (uint32_t)t.slots++; };
-    auto level_of = [&](uint32_t x) { return (x & TAPE_CONST) ? 0u : slot_level[x]; };
+    auto level_of = [&](uint32_t x) { return (x & tags) ? 0u : slot_level[x]; };
     auto emit = [&](uint32_t kind, uint32_t dst, uint32_t a, uint32_t b) {
         const uint32_t lv = 1 + std::max(level_of(a), level_of(b));
         t.ops.push_back({dst, a, b, kind});
@@ -323,6 +319,7 @@ static void built_compile_tape(zk_circuit& c) {
         return dst;
     };
     const Fr one = Fr::one();
+    auto copy = [&](uint32_t x) { return emit(TAPE_COPY, fresh(), x, constant(Fr::zero())); };   // (b is not read)
     auto side = [&](uint32_t from, uint32_t to) {
         uint32_t acc = 0;
         bool any = false;
@@ -330,8 +327,8 @@ static void built_compile_tape(zk_circuit& c) {
             const BuiltTerm& x = p.terms[e];
             uint32_t v;
             if (x.wit == 0) v = constant(x.w);
-            else if (x.w == one) v = x.wit;
-            else v = emit(TAPE_MUL, fresh(), constant(x.w), x.wit);
+            else if (x.w == one) v = ref(x.wit, copy);
+            else v = emit(TAPE_MUL, fresh(), constant(x.w), ref(x.wit, copy));
             acc = any ? emit(TAPE_ADD, fresh(), acc, v) : v;
             any = true;
         }
@@ -343,16 +340,36 @@ static void built_compile_tape(zk_circuit& c) {
             if (p.terms[s.l0 + i].wit != p.terms[s.r0 + i].wit || p.terms[s.l0 + i].w != p.terms[s.r0 + i].w) return false;
         return true;
     };
+    for (size_t k = 0; k < p.subs.size(); ++k) {
+        const BuiltSub& s = p.subs[k];
+        if (s.out == WIT_NONE || !take(k)) continue;   // an assertion computes nothing
+        const uint32_t l = side(s.l0, s.r0);
+        const uint32_t r = same_sides(s) ? l : side(s.r0, s.end);
+        emit(TAPE_MUL, ref(s.out, copy), l, r);
+    }
+    return op_level;
+}
+
+// The whole circuit as the tape of witgen.hip: slot = witness index, temporaries behind the witness.
+static void built_compile_tape(zk_circuit& c) {
+    const Built& p = *c.built;
+    Tape& t = c.tape;
+    const size_t m = c.u.size();
+    t.n_in = p.in_wit.size();
+    t.m = m;
+    t.slots = m;
+    t.in_slot = p.in_wit;
+    t.in_bit.resize(t.n_in);
+    for (size_t i = 0; i < t.n_in; ++i) t.in_bit[i] = p.in_bit[i] ? p.in_wire[i] + 1 : 0;
+    const std::vector<uint32_t> op_level = built_compile_subs(p, t, TAPE_CONST, [](size_t) { return true; }, [](uint32_t i, auto&&) { return i; });
+    std::vector<uint32_t> node_level(m, 0), per_level;
     for (const BuiltSub& s : p.subs) {
-        if (s.out == WIT_NONE) continue;              // an assertion computes nothing
+        if (s.out == WIT_NONE) continue;
         uint32_t node = 0;
         for (uint32_t e = s.l0; e < s.end; ++e) node = std::max(node, node_level[p.terms[e].wit]);
         node_level[s.out] = ++node;
         if (per_level.size() < node) per_level.resize(node, 0);
         ++per_level[node - 1];
-        const uint32_t l = side(s.l0, s.r0);
-        const uint32_t r = same_sides(s) ? l : side(s.r0, s.end);
-        emit(TAPE_MUL, s.out, l, r);
     }
     if (t.slots >= TAPE_CONST || t.ops.size() >= TAPE_CONST) {
         t.status = ZK_ERR_SIZE;
@@ -364,6 +381,70 @@ static void built_compile_tape(zk_circuit& c) {
     t.depth = per_level.size();
     for (uint32_t n : per_level) t.width = std::max<size_t>(t.width, n);
     t.level_ptr = sort_by_level(t.ops, op_level);
+}
+
+// The split into a boolean core and a field tail (circuit.hpp: Mixed), for every built circuit.  `wit` maps the builder's wire ids
+// to witness indices; b.subs and p.subs run in parallel.
+static void built_split(zk_circuit& c, const zk_builder& b, const std::vector<uint32_t>& wit) {
+    Built& p = *c.built;
+    Mixed& x = p.mix;
+    Tape& t = x.tail;
+    const size_t m = c.u.size();
+    const char* too_large = "builder: circuit too large: its indices leave no room for the operand tags of the field tail";
+    if (m + 1 >= MIX_BIT || p.pack_out.size() >= MIX_BIT) throw ParseError{ZK_ERR_SIZE, too_large};
+    auto idx = [&](uint32_t wire) { return wit[wire] == WIT_NONE ? (uint32_t)m : wit[wire]; };   // index m stands for the constant 0
+    x.field.assign(m + 1, 0);
+    std::vector<uint32_t> ref(m, 0);                          // per witness index: its operand word in the tail
+    for (size_t i = 0; i < m; ++i) ref[i] = MIX_BIT | (uint32_t)i;
+    auto new_slot = [&](uint32_t index) {
+        x.field[index] = 1;
+        ref[index] = (uint32_t)x.slot_wit.size();
+        x.slot_wit.push_back(index);
+    };
+    for (size_t i = 0; i < p.in_wit.size(); ++i) {
+        if (p.in_bit[i]) { x.bit_in_wit.push_back(p.in_wit[i]); continue; }
+        t.in_slot.push_back((uint32_t)x.slot_wit.size());
+        new_slot(p.in_wit[i]);
+    }
+    t.n_in = t.in_slot.size();
+    std::vector<uint32_t> level(m + 1, 0), op_level;
+    std::vector<uint8_t> in_tail(b.subs.size(), 0);
+    for (size_t k = 0; k < b.subs.size(); ++k) {
+        const zk_builder::Sub& s = b.subs[k];
+        if (s.out == WIT_NONE) continue;
+        const uint32_t out = wit[s.out];
+        if (s.bkind <= BOOL_GREATER && !x.field[idx(s.a)] && !x.field[idx(s.b)]) {
+            const BoolOp op{out, idx(s.a), idx(s.b), s.bkind};
+            const uint32_t lv = 1 + std::max(level[op.a], level[op.b]);
+            level[out] = lv;
+            x.core_ops.push_back(op);
+            op_level.push_back(lv);
+            continue;
+        }
+        bool core = s.bkind == BOOL_PACK;
+        for (uint32_t e = s.l0; core && e < s.r0; ++e) core = !x.field[idx(b.terms[e].wire)];
+        if (s.bkind == BOOL_PACK) x.pack_core.push_back(core);
+        if (core) {                                           // gathered from the operands' bits: no tail slot
+            x.field[out] = 1;
+            ref[out] = MIX_PACK | (uint32_t)x.cpack_out.size();
+            x.cpack_out.push_back(out);
+            for (uint32_t e = s.l0; e < s.r0; ++e) x.cpack_bits.push_back(idx(b.terms[e].wire));
+            x.cpack_ptr.push_back((uint32_t)x.cpack_bits.size());
+        } else {
+            new_slot(out);
+            in_tail[k] = 1;
+        }
+    }
+    x.core_level_ptr = sort_by_level(x.core_ops, op_level);
+    t.m = m;
+    t.slots = x.slot_wit.size();
+    const std::vector<uint32_t> tail_level = built_compile_subs(p, t, MIX_TAG, [&](size_t k) { return in_tail[k] != 0; },
+                                                                 [&](uint32_t i, auto&& copy) {   // a core pack is gathered once, at its first reader
+                                                                     if ((ref[i] & MIX_TAG) == MIX_PACK) ref[i] = copy(ref[i]);
+                                                                     return ref[i];
+                                                                 });
+    if (t.slots >= MIX_BIT || t.ops.size() >= MIX_BIT || t.consts.size() >= MIX_BIT) throw ParseError{ZK_ERR_SIZE, too_large};
+    t.level_ptr = sort_by_level(t.ops, tail_level);
 }
 
 static zk_circuit* builder_finish(zk_builder& b, const uint32_t* verify, size_t n_verify) {
@@ -447,6 +528,7 @@ static zk_circuit* builder_finish(zk_builder& b, const uint32_t* verify, size_t 
         p.bool_level_ptr = sort_by_level(p.bool_ops, op_level);
     }
     built_compile_tape(*c);
+    built_split(*c, b, wit);
     b.finished = true;
     b.terms.clear(); b.terms.shrink_to_fit();
     b.subs.clear(); b.subs.shrink_to_fit();
@@ -480,6 +562,52 @@ static void built_weights(const zk_circuit& c, const uint64_t* inputs, size_t n_
         vals[s.out] = l * r;
     }
     for (size_t i = 0; i < m; ++i) fr_to_words(vals[i].to_canonical(), out + 4 * i);
+}
+
+// One witness through the split (circuit.hpp: Mixed): what mixgen.hip's kernels compute for one instance, without a GPU.  Bit inputs
+// are bits (bit k of in_bits = the k-th ZK_WIRE_BIT input), the core is uint64_t logic on one word whose bit 0 is the instance, a
+// core pack is its operands' bits gathered, the tail runs over Fr.  Field inputs: 4 canonical words each, in input order.
+static void mixed_run_host(const zk_circuit& c, const uint8_t* in_bits, size_t n_bit_bytes, const uint64_t* in_fields, size_t n_field, uint64_t* out,
+                           size_t m) {
+    const Mixed& x = c.built->mix;
+    const Tape& t = x.tail;
+    auto serr = [](const std::string& s) { return ParseError{ZK_ERR_ARG, "StructureErr(None, " + s + ")"}; };
+    if (n_bit_bytes != (x.bit_in_wit.size() + 7) / 8 || n_field != t.n_in) throw serr("Wrong number of values supplied");
+    if (m != c.u.size()) throw serr("weights buffer size mismatch");
+    for (size_t i = 0; i < n_field; ++i)
+        if (!fr_from_words(in_fields + 4 * i).raw_in_range()) throw ParseError{ZK_ERR_RANGE, "input value >= r"};
+    std::vector<uint64_t> state(m + 1, 0);
+    state[0] = ~0ull;
+    for (size_t k = 0; k < x.bit_in_wit.size(); ++k) state[x.bit_in_wit[k]] = (in_bits[k / 8] >> (k % 8)) & 1 ? ~0ull : 0;
+    for (const BoolOp& op : x.core_ops) state[op.dst] = bool_apply(op.kind, state[op.a], state[op.b]);
+    auto gather = [&](uint32_t pk, uint64_t* w) {
+        w[0] = w[1] = w[2] = w[3] = 0;
+        for (uint32_t e = x.cpack_ptr[pk]; e < x.cpack_ptr[pk + 1]; ++e) {
+            const uint32_t at = e - x.cpack_ptr[pk];
+            w[at / 64] |= (state[x.cpack_bits[e]] & 1) << (at % 64);
+        }
+    };
+    std::vector<Fr> vals(t.slots);
+    for (size_t i = 0; i < n_field; ++i) vals[t.in_slot[i]] = Fr::from_canonical(fr_from_words(in_fields + 4 * i));
+    auto operand = [&](uint32_t r) {
+        const uint32_t i = r & MIX_INDEX;
+        switch (r & MIX_TAG) {
+            case TAPE_CONST: return t.consts[i];
+            case MIX_BIT: return state[i] & 1 ? Fr::one() : Fr::zero();
+            case MIX_PACK: { uint64_t w[4]; gather(i, w); return Fr::from_canonical(fr_from_words(w)); }
+            default: return vals[i];
+        }
+    };
+    for (const TapeOp& op : t.ops) {
+        const Fr a = operand(op.a), b = operand(op.b);
+        vals[op.dst] = op.kind == TAPE_COPY ? a : op.kind == TAPE_MUL ? a * b : a + b;
+    }
+    for (size_t i = 0; i < m; ++i) {
+        out[4 * i] = state[i] & 1;
+        out[4 * i + 1] = out[4 * i + 2] = out[4 * i + 3] = 0;
+    }
+    for (size_t pk = 0; pk < x.cpack_out.size(); ++pk) gather((uint32_t)pk, out + 4 * (size_t)x.cpack_out[pk]);
+    for (size_t s = 0; s < x.slot_wit.size(); ++s) fr_to_words(vals[s].to_canonical(), out + 4 * (size_t)x.slot_wit[s]);
 }
 
 }  // namespace zk

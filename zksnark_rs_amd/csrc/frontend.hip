@@ -683,6 +683,34 @@ int zk_circuit_qap_sparse_unity(zk_ctx* ctx, const zk_circuit* c, zk_qap** out) 
     return guarded(ctx, [&] { *out = circuit_to_qap_sparse(ctx, *c, true); });
 }
 int zk_circuit_is_boolean(const zk_circuit* c) { return c && c->built && c->built->boolean ? 1 : 0; }
+int zk_circuit_mixed_dims(const zk_circuit* c, size_t* n_bit_inputs, size_t* n_field_inputs, size_t* core_ops, size_t* core_levels, size_t* tail_ops,
+                          size_t* tail_levels, size_t* tail_slots) {
+    if (!c) return ZK_ERR_ARG;
+    if (!c->built) {
+        const_cast<zk_circuit*>(c)->last_error = "a parsed program has no boolean core: the split exists for built circuits (zk_builder_finish)";
+        return ZK_ERR_UNSUPPORTED;
+    }
+    const Mixed& x = c->built->mix;
+    if (n_bit_inputs) *n_bit_inputs = x.bit_in_wit.size();
+    if (n_field_inputs) *n_field_inputs = x.tail.n_in;
+    if (core_ops) *core_ops = x.core_ops.size();
+    if (core_levels) *core_levels = x.core_level_ptr.size() - 1;
+    if (tail_ops) *tail_ops = x.tail.ops.size();
+    if (tail_levels) *tail_levels = x.tail.levels();
+    if (tail_slots) *tail_slots = x.tail.slots;
+    return ZK_OK;
+}
+int zk_circuit_weights_mixed(const zk_circuit* c, const uint8_t* in_bits, size_t n_bit_bytes, const uint64_t* in_fields, size_t n_field,
+                             uint64_t* weights_out, size_t m) {
+    if (!c || !weights_out || (n_bit_bytes && !in_bits) || (n_field && !in_fields)) return ZK_ERR_ARG;
+    std::string msg;
+    int rc = front_guard(&msg, [&] {
+        if (!c->built) throw ParseError{ZK_ERR_UNSUPPORTED, "a parsed program has no boolean core: use zk_circuit_weights or zk_circuit_weights_tape"};
+        mixed_run_host(*c, in_bits, n_bit_bytes, in_fields, n_field, weights_out, m);
+    });
+    const_cast<zk_circuit*>(c)->last_error = msg;
+    return rc;
+}
 int zk_circuit_packed_wires(const zk_circuit* c, size_t* count) {
     if (!c || !count) return ZK_ERR_ARG;
     *count = c->built ? c->built->pack_out.size() : 0;

@@ -13,7 +13,7 @@
 //   store      slots 0..m-1 to canonical form, instance-major (what zk_prove_dev / zk_prove_batch_submit take per witness)
 // Lanes behind `count` in the last group never return early: they take part in every barrier and are predicated off every load and
 // store.  Groups run in chunks of as many as the scratch cap holds (option "witgen_scratch_kib"), so `count` is not bounded by memory.
-#include "pipeline.hpp"
+#include "witgen_kernels.cuh"
 #include "circuit.hpp"
 
 struct zk_witgen {
@@ -31,54 +31,13 @@ struct zk_witgen {
 
 namespace zk {
 
-static constexpr int WG_LANES = 64;
-static constexpr unsigned WG_MAX_WAVES = 4;
-static constexpr unsigned long long WG_NO_ERROR = ~0ull;
-
-// The W rule: W = the mean number of operations per level, rounded up to a power of two, at most 4 (and at most the widest level).
-// A level of `width` operations costs ceil(width / W) rounds and every level one barrier; waves beyond the mean width would wait at
-// barriers most of the time, and parallelism beyond one group comes from the other groups.  A chain (every level 1 wide) gets W = 1.
-static unsigned witgen_waves(const Tape& t) {
-    const size_t levels = t.levels();
-    if (!levels) return 1;
-    const size_t mean = (t.ops.size() + levels - 1) / levels;
-    unsigned w = 1;
-    while (w < mean && w < WG_MAX_WAVES) w *= 2;
-    while (w > 1 && w / 2 >= t.max_level_width()) w /= 2;
-    return w;
-}
-
-__device__ __forceinline__ Fr witgen_operand(uint32_t x, const Fr* __restrict__ consts, const Fr* sc) {
-    return (x & TAPE_CONST) ? consts[x & ~TAPE_CONST] : sc[(size_t)x * WG_LANES];
-}
-// Operations begin, begin + stride, ... < end in this order, each reading what the ones before it in the run (and before the run)
-// wrote.  The operands of the next operation are requested BEFORE the current one is computed, so that their memory latency passes
-// under a field multiplication instead of in front of it; where the next operation reads the current result (every step of a chain)
-// the value is handed over in registers and the early load is dropped.  Without this a dependent chain pays store -> load through
-// the cache per operation: 2.8 us per operation measured on the 2^16-gate chain, one wave per group.
-__device__ __forceinline__ void witgen_run_ops(const TapeOp* __restrict__ ops, uint32_t begin, uint32_t end, uint32_t stride,
-                                               const Fr* __restrict__ consts, Fr* sc) {
-    if (begin >= end) return;
-    TapeOp cur = ops[begin];
-    Fr a = witgen_operand(cur.a, consts, sc), b = witgen_operand(cur.b, consts, sc);
-    for (uint32_t k = begin; k < end; k += stride) {
-        const bool more = k + stride < end;
-        TapeOp nxt = cur;
-        Fr na = a, nb = b;
-        if (more) {
-            nxt = ops[k + stride];
-            na = witgen_operand(nxt.a, consts, sc);
-            nb = witgen_operand(nxt.b, consts, sc);
-        }
-        const Fr r = cur.kind == TAPE_COPY ? a : cur.kind == TAPE_MUL ? a * b : a + b;
-        sc[(size_t)cur.dst * WG_LANES] = r;
-        if (!(nxt.a & TAPE_CONST) && nxt.a == cur.dst) na = r;
-        if (!(nxt.b & TAPE_CONST) && nxt.b == cur.dst) nb = r;
-        cur = nxt;
-        a = na;
-        b = nb;
-    }
-}
+// an operand of the whole-circuit tape: a pooled constant or a slot of the lane's scratch (run: witgen_kernels.cuh)
+struct WitgenFetch {
+    const Fr* __restrict__ consts;
+    const Fr* sc;
+    __device__ __forceinline__ bool is_slot(uint32_t x) const { return !(x & TAPE_CONST); }
+    __device__ __forceinline__ Fr operator()(uint32_t x) const { return (x & TAPE_CONST) ? consts[x & ~TAPE_CONST] : sc[(size_t)x * WG_LANES]; }
+};
 
 __global__ void __launch_bounds__(WG_LANES * WG_MAX_WAVES)
 k_witgen(const TapeOp* __restrict__ ops, const uint32_t* __restrict__ level_ptr, unsigned levels, const uint32_t* __restrict__ in_slot,
@@ -106,11 +65,12 @@ k_witgen(const TapeOp* __restrict__ ops, const uint32_t* __restrict__ level_ptr,
     }
     if (W > 1) __syncthreads();
 
+    const WitgenFetch fetch{consts, sc};
     if (W == 1) {                       // one wave, program order: the whole tape as one run, no barrier
-        if (live) witgen_run_ops(ops, 0, level_ptr[levels], 1, consts, sc);
+        if (live) witgen_run_ops(ops, 0, level_ptr[levels], 1, sc, fetch);
     } else {
         for (unsigned l = 0; l < levels; ++l) {
-            if (live) witgen_run_ops(ops, level_ptr[l] + wave, level_ptr[l + 1], W, consts, sc);
+            if (live) witgen_run_ops(ops, level_ptr[l] + wave, level_ptr[l + 1], W, sc, fetch);
             __syncthreads();
         }
     }
