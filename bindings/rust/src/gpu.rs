@@ -192,6 +192,8 @@ extern "C" {
                          out_wires: *mut u32, out_bytes: usize) -> c_int;
     fn zk_builder_assert_bit(b: *mut ZkBuilder, wire: u32) -> c_int;
     fn zk_builder_pack(b: *mut ZkBuilder, bits: *const u32, n_bits: usize, out: *mut u32) -> c_int;
+    fn zk_builder_poseidon(b: *mut ZkBuilder, in_wires: *const u32, arity: usize, out: *mut u32) -> c_int;
+    fn zk_builder_merkle_root(b: *mut ZkBuilder, leaf: u32, siblings: *const u32, dirs: *const u32, depth: usize, out: *mut u32) -> c_int;
     fn zk_builder_finish(b: *mut ZkBuilder, verify_wires: *const u32, n_verify: usize, out: *mut *mut ZkCircuit) -> c_int;
     fn zk_circuit_is_boolean(c: *const ZkCircuit) -> c_int;
     fn zk_circuit_packed_wires(c: *const ZkCircuit, count: *mut usize) -> c_int;
@@ -207,6 +209,17 @@ extern "C" {
                      d_weights_out: *mut c_void, m: usize) -> c_int;
     fn zk_mixgen_eval_fields(g: *mut ZkMixgen, d_in_bits: *const c_void, in_stride_bytes: usize, d_in_fields: *const c_void, count: usize,
                              wires: *const u32, n_wires: usize, d_out_words: *mut c_void) -> c_int;
+    // Poseidon over Fr (circomlib's parameter sets): host hash, GPU batch hashing, a device-resident Merkle tree and its paths
+    fn zk_poseidon_hash(inputs: *const u64, arity: usize, out: *mut u64) -> c_int;
+    fn zk_poseidon_params(arity: usize, rf: *mut c_uint, rp: *mut c_uint, round_constants: *mut u64, mds: *mut u64) -> c_int;
+    fn zk_poseidon_hash_batch(ctx: *mut ZkCtx, d_inputs: *const c_void, arity: usize, count: usize, d_out: *mut c_void) -> c_int;
+    fn zk_poseidon_tree_build(ctx: *mut ZkCtx, d_leaves: *const c_void, n_leaves: usize, depth: c_uint, out: *mut *mut ZkPoseidonTree) -> c_int;
+    fn zk_poseidon_tree_free(t: *mut ZkPoseidonTree);
+    fn zk_poseidon_tree_root(t: *const ZkPoseidonTree, out: *mut u64) -> c_int;
+    fn zk_poseidon_tree_dims(t: *const ZkPoseidonTree, n_leaves: *mut usize, depth: *mut c_uint) -> c_int;
+    fn zk_poseidon_tree_nodes(t: *const ZkPoseidonTree, level: c_uint, out: *mut u64) -> c_int;
+    fn zk_poseidon_tree_paths(t: *mut ZkPoseidonTree, d_indices: *const c_void, count: usize, d_fields_out: *mut c_void, field_stride_words: usize,
+                              d_bits_out: *mut c_void, bits_stride_bytes: usize) -> c_int;
     fn zk_boolgen_create(ctx: *mut ZkCtx, c: *const ZkCircuit, out: *mut *mut ZkBoolgen) -> c_int;
     fn zk_boolgen_free(g: *mut ZkBoolgen);
     fn zk_boolgen_run(g: *mut ZkBoolgen, d_in_bits: *const c_void, in_stride_bytes: usize, count: usize, d_weights_out: *mut c_void,
@@ -272,6 +285,7 @@ extern "C" {
 #[repr(C)] pub struct ZkBuilder { _p: [u8; 0] }
 #[repr(C)] pub struct ZkBoolgen { _p: [u8; 0] }
 #[repr(C)] pub struct ZkMixgen { _p: [u8; 0] }
+#[repr(C)] pub struct ZkPoseidonTree { _p: [u8; 0] }
 #[repr(C)] pub struct ZkMgpu { _p: [u8; 0] }
 
 fn check(ctx: *mut ZkCtx, rc: c_int) {
@@ -1287,6 +1301,19 @@ impl GpuCircuitBuilder {
         self.ok(unsafe { zk_builder_pack(self.0, bits.as_ptr(), bits.len(), &mut out) });
         out
     }
+    /// Poseidon of 1, 2 or 4 wires: 217 / 244 / 301 general sub-circuits over linear forms; the output is a field element
+    pub fn poseidon(&mut self, inputs: &[WireId]) -> WireId {
+        let mut out = 0u32;
+        self.ok(unsafe { zk_builder_poseidon(self.0, inputs.as_ptr(), inputs.len(), &mut out) });
+        out
+    }
+    /// the root of the Merkle path leaf, siblings[k], dirs[k] (1: the right child at level k): 246 gates a level
+    pub fn merkle_root(&mut self, leaf: WireId, siblings: &[WireId], dirs: &[WireId]) -> WireId {
+        assert!(siblings.len() == dirs.len());
+        let mut out = 0u32;
+        self.ok(unsafe { zk_builder_merkle_root(self.0, leaf, siblings.as_ptr(), dirs.as_ptr(), dirs.len(), &mut out) });
+        out
+    }
     pub fn fan_in(&mut self, inputs: &[WireId], g: Gate) -> WireId {
         let mut out = 0u32;
         self.ok(unsafe { zk_builder_fan_in(self.0, g as c_int, inputs.as_ptr(), inputs.len(), &mut out) });
@@ -1424,6 +1451,50 @@ impl Mixgen {
         unsafe {
             check(self.ctx, zk_mixgen_eval_fields(self.g, d_in_bits, in_stride_bytes, d_in_fields, count, wires.as_ptr(), wires.len(), d_out_words))
         }
+    }
+}
+
+/// zk_poseidon_hash: Poseidon of 1, 2 or 4 elements on the host; None for another arity or an input >= r
+pub fn poseidon_hash(inputs: &[[u64; 4]]) -> Option<[u64; 4]> {
+    let mut out = [0u64; 4];
+    if unsafe { zk_poseidon_hash(inputs.as_ptr() as *const u64, inputs.len(), out.as_mut_ptr()) } == 0 { Some(out) } else { None }
+}
+/// zk_poseidon_hash_batch: `count` hashes of `arity` elements each, device to device
+pub fn poseidon_hash_batch(ctx: *mut ZkCtx, d_inputs: *const c_void, arity: usize, count: usize, d_out: *mut c_void) {
+    unsafe { check(ctx, zk_poseidon_hash_batch(ctx, d_inputs, arity, count, d_out)) }
+}
+
+/// zk_poseidon_tree_*: a binary Merkle tree over Poseidon of arity 2 that stays on the device; paths() writes leaf | siblings and the
+/// direction bits in the layout Mixgen::run reads as d_in_fields and d_in_bits
+pub struct PoseidonTree { ctx: *mut ZkCtx, t: *mut ZkPoseidonTree }
+impl Drop for PoseidonTree { fn drop(&mut self) { unsafe { zk_poseidon_tree_free(self.t) } } }
+impl PoseidonTree {
+    pub fn build(ctx: *mut ZkCtx, d_leaves: *const c_void, n_leaves: usize, depth: u32) -> Self {
+        let mut t: *mut ZkPoseidonTree = std::ptr::null_mut();
+        unsafe { check(ctx, zk_poseidon_tree_build(ctx, d_leaves, n_leaves, depth as c_uint, &mut t)) };
+        PoseidonTree { ctx, t }
+    }
+    pub fn root(&self) -> [u64; 4] {
+        let mut out = [0u64; 4];
+        unsafe { check(self.ctx, zk_poseidon_tree_root(self.t, out.as_mut_ptr())) };
+        out
+    }
+    /// (n_leaves, depth)
+    pub fn dims(&self) -> (usize, u32) {
+        let (mut n, mut d) = (0usize, 0 as c_uint);
+        unsafe { check(self.ctx, zk_poseidon_tree_dims(self.t, &mut n, &mut d)) };
+        (n, d as u32)
+    }
+    pub fn nodes(&self, level: u32) -> Vec<[u64; 4]> {
+        let (n, _) = self.dims();
+        let size = if level == 0 { n } else { std::cmp::max(1, (n + (1usize << level) - 1) >> level) };
+        let mut out = vec![[0u64; 4]; size];
+        unsafe { check(self.ctx, zk_poseidon_tree_nodes(self.t, level as c_uint, out.as_mut_ptr() as *mut u64)) };
+        out
+    }
+    pub fn paths(&self, d_indices: *const c_void, count: usize, d_fields_out: *mut c_void, field_stride_words: usize, d_bits_out: *mut c_void,
+                 bits_stride_bytes: usize) {
+        unsafe { check(self.ctx, zk_poseidon_tree_paths(self.t, d_indices, count, d_fields_out, field_stride_words, d_bits_out, bits_stride_bytes)) }
     }
 }
 

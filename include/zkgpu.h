@@ -398,6 +398,19 @@ int zk_builder_assert_bit(zk_builder* b, uint32_t wire);
  * comparator or the sponge is legal and sends the circuit to the tape (zk_witgen_*), as zk_builder_sub_circuit does. */
 #define ZK_PACK_MAX_BITS 253
 int zk_builder_pack(zk_builder* b, const uint32_t* bits, size_t n_bits, uint32_t* out);
+/* *out = Poseidon(in_wires[0 .. arity)) (see "Poseidon" below), arity 1, 2 or 4.  The state is t = arity + 1 linear forms over wires
+ * (one term per wire, weights mod r, the constant on ZK_WIRE_ONE); an S-box on a form L is three sub-circuits L * L = a, a * a = c,
+ * c * L = e; round constants and the mix are folded into the forms and cost no gate; one closing sub-circuit (state[0]) * 1 = out
+ * makes the digest a wire.  Exactly 3 (8 t + R_P) + 1 gates: 217, 244, 301 for arity 1, 2, 4; a side has at most t + R_P + 1 terms.
+ * Inputs may be any known wire, constants and bit wires included, and a wire may repeat.  The output is field-class: the circuit is
+ * not boolean and goes to the tape or the mixed path, as zk_builder_sub_circuit does.  ZK_ERR_ARG with text: another arity, an
+ * unknown wire, a null pointer. */
+int zk_builder_poseidon(zk_builder* b, const uint32_t* in_wires, size_t arity, uint32_t* out);
+/* *out = the root of the Merkle path from `leaf` through siblings[0 .. depth) (the sibling of level k) with direction wires
+ * dirs[0 .. depth) (1: the path's node is the RIGHT child at level k), over Poseidon of arity 2: what zk_poseidon_tree_paths hands
+ * out.  Per level: zk_builder_assert_bit(dir), one gate dir * (sib - cur) = d, and Poseidon of the forms (cur + d, sib - d) -- 246
+ * gates.  depth == 0: *out = leaf, nothing is emitted.  ZK_ERR_ARG with text: an unknown wire, a null array. */
+int zk_builder_merkle_root(zk_builder* b, uint32_t leaf, const uint32_t* siblings, const uint32_t* dirs, size_t depth, uint32_t* out);
 /* The circuit as an ordinary zk_circuit (free it with zk_circuit_free; the builder may be freed before or after).  Witness order: the
  * constant 1, the verify wires in the order given (qap.input = n_verify), the remaining input wires in creation order, the remaining
  * wires by id.  Sub-circuit k is gate k (0-based), at root k + 1 of zk_circuit_qap / _qap_sparse.  ZK_ERR_ARG with text: a verify wire
@@ -493,6 +506,55 @@ int zk_mixgen_run(zk_mixgen* g, const void* d_in_bits, size_t in_stride_bytes, c
  * Nothing is expanded and nothing else is written.  Errors as zk_mixgen_run; an index >= m: ZK_ERR_ARG. */
 int zk_mixgen_eval_fields(zk_mixgen* g, const void* d_in_bits, size_t in_stride_bytes, const void* d_in_fields, size_t count,
                           const uint32_t* wires, size_t n_wires, void* d_out_words);
+
+/* ------------------------------------------------------------------------------------------
+ * Poseidon over the BN254 scalar field (csrc/poseidon.hpp, csrc/poseidon.hip): host hash, circuit gadgets, GPU batch hashing and a
+ * device-resident Merkle tree.  S-box x^5, state width t = arity + 1, arity 1, 2 or 4; R_F = 8 full rounds, R_P = 56 / 57 / 60
+ * partial rounds: circomlib's parameter sets, so digests are those of circom, snarkjs and Semaphore.
+ *   hash(inputs): state = [0, inputs...]; per round rho: add C[rho * t + i] to element i; x^5 on every element if rho < 4 or
+ *   rho >= 4 + R_P, else on element 0 only; state = M * state.  The digest is element 0 after the last round.
+ * C and M are generated in code from the Poseidon paper's Grain LFSR (csrc/poseidon.hpp has the procedure).  Any other arity:
+ * ZK_ERR_ARG (with text where the call has a handle that keeps one).
+ * ---------------------------------------------------------------------------------------- */
+/* One hash on the host, no context.  inputs: arity x 4 canonical words; out: 4 canonical words.  ZK_ERR_ARG: a null pointer, an
+ * arity other than 1, 2, 4.  ZK_ERR_RANGE: an input >= r. */
+int zk_poseidon_hash(const uint64_t* inputs, size_t arity, uint64_t out[4]);
+/* The parameters of one arity, canonical words: *rf = 8, *rp, round_constants[(rf + rp) * t * 4] (C[rho * t + i] at element
+ * rho * t + i), mds[t * t * 4] (M[i][j] at element i * t + j), t = arity + 1.  Any pointer may be NULL.  ZK_ERR_ARG: the arity. */
+int zk_poseidon_params(size_t arity, unsigned* rf, unsigned* rp, uint64_t* round_constants, uint64_t* mds);
+/* `count` hashes on the GPU, one per lane.  d_inputs: count x arity x 4 canonical words, instance-major; d_out: count x 4 canonical
+ * words.  Both device pointers, 16-byte aligned.  Complete on return.  count == 0: ZK_OK, nothing touched.  ZK_ERR_ARG: the arity, a
+ * null or misaligned pointer.  An input word pattern >= r: ZK_ERR_RANGE, found on the device; zk_last_error names the LOWEST such
+ * instance and the contents of d_out are unspecified.  The parameters are uploaded once per context and arity. */
+int zk_poseidon_hash_batch(zk_ctx* ctx, const void* d_inputs, size_t arity, size_t count, void* d_out);
+/* A binary Merkle tree (arity 2) that stays on the device.  Level 0 is the leaves, level k holds ceil(n_leaves / 2^k) nodes, at
+ * least one from level 1 up, level `depth` is the root.  A child that does not exist counts as the zero hash of its level: z_0 = 0,
+ * z_{k+1} = hash(z_k, z_k) -- so a tree of depth 20 over 1000 leaves stores about 2000 nodes, not 2^21, and n_leaves == 0 gives
+ * root = z_depth.  d_leaves: n_leaves x 4 canonical words on the device (copied; may be NULL when n_leaves == 0).  One kernel launch
+ * per level; complete on return.  The context must outlive the tree.  ZK_ERR_ARG with text: depth > 32, n_leaves > 2^depth, a null
+ * pointer.  ZK_ERR_RANGE with text naming the lowest such leaf: a leaf >= r.  *out is NULL on every failure.  A built tree is not
+ * updated or appended to. */
+typedef struct zk_poseidon_tree zk_poseidon_tree;
+int zk_poseidon_tree_build(zk_ctx* ctx, const void* d_leaves, size_t n_leaves, unsigned depth, zk_poseidon_tree** out);
+void zk_poseidon_tree_free(zk_poseidon_tree* t);     /* NULL is a no-op */
+/* the root, 4 canonical words (kept on the host by zk_poseidon_tree_build) */
+int zk_poseidon_tree_root(const zk_poseidon_tree* t, uint64_t out[4]);
+/* either pointer may be NULL */
+int zk_poseidon_tree_dims(const zk_poseidon_tree* t, size_t* n_leaves, unsigned* depth);
+/* downloads the stored nodes of one level to the host: out[size x 4] canonical words, size = n_leaves for level 0 and
+ * max(1, ceil(n_leaves / 2^level)) above.  ZK_ERR_ARG with text: level > depth. */
+int zk_poseidon_tree_nodes(const zk_poseidon_tree* t, unsigned level, uint64_t* out);
+/* Authentication paths of `count` leaves, in the layout zk_mixgen_run reads.  d_indices: count uint64 leaf indices on the device.
+ * For instance j, at d_fields_out + j * field_stride_words words: the leaf, then the siblings of levels 0 .. depth - 1,
+ * (1 + depth) x 4 canonical words (a sibling the tree does not store is z_k); at d_bits_out + j * bits_stride_bytes bytes: the
+ * direction bits, bit k = (index >> k) & 1 (1: the path's node is the RIGHT child at level k), packed as zk_mixgen_run takes bit
+ * inputs, ceil(depth / 8) bytes -- the index's own low bytes.  For a circuit whose inputs were created in the order leaf, siblings,
+ * directions (zk_builder_merkle_root) the two outputs are d_in_fields and d_in_bits of zk_mixgen_run with no host step between.
+ * All device pointers, 8-byte aligned (d_bits_out: any; may be NULL at depth 0).  One gather kernel; complete on return.
+ * count == 0: ZK_OK.  ZK_ERR_ARG with text: field_stride_words < (1 + depth) * 4, bits_stride_bytes < ceil(depth / 8), a null
+ * pointer.  ZK_ERR_RANGE with text naming the lowest such instance: an index >= n_leaves; the outputs are then unspecified. */
+int zk_poseidon_tree_paths(zk_poseidon_tree* t, const void* d_indices, size_t count, void* d_fields_out, size_t field_stride_words,
+                           void* d_bits_out, size_t bits_stride_bytes);
 
 /* ------------------------------------------------------------------------------------------
  * CRS  (SigmaG1 / SigmaG2, groth16/mod.rs:105-121)

@@ -334,6 +334,18 @@ class Circuit {
     template <class Wires>
     WireId pack(const Wires& bits) { WireId o; check(zk_builder_pack(b_, bits.data(), bits.size(), &o)); return o; }
 
+    // Poseidon of 1, 2 or 4 wires (poseidon::hash on their values): 217 / 244 / 301 general sub-circuits; the output is a field element
+    template <class Wires>
+    WireId poseidon(const Wires& inputs) { WireId o; check(zk_builder_poseidon(b_, inputs.data(), inputs.size(), &o)); return o; }
+    // the root of the Merkle path leaf, siblings[k], dirs[k] (1: the right child at level k) over Poseidon of arity 2: 246 gates a level
+    template <class Wires>
+    WireId merkle_root(WireId leaf, const Wires& siblings, const Wires& dirs) {
+        if (siblings.size() != dirs.size()) throw Error(ZK_ERR_ARG, "merkle_root: one direction per sibling");
+        WireId o;
+        check(zk_builder_merkle_root(b_, leaf, siblings.data(), dirs.data(), dirs.size(), &o));
+        return o;
+    }
+
     template <class Wires>
     WireId fan_in(const Wires& inputs, Gate g) { WireId o; check(zk_builder_fan_in(b_, (int)g, inputs.data(), inputs.size(), &o)); return o; }
     template <class Wires>
@@ -449,6 +461,54 @@ class Mixgen {
    private:
     const Context& c_;
     zk_mixgen* g_ = nullptr;
+};
+
+// Poseidon over Fr, circomlib's parameter sets (zk_poseidon_*): hash of 1, 2 or 4 elements on the host, `count` hashes on the device
+namespace poseidon {
+inline FrLocal hash(const std::vector<FrLocal>& inputs) {
+    FrLocal out;
+    const int rc = zk_poseidon_hash(inputs.empty() ? nullptr : inputs[0].w.data(), inputs.size(), out.w.data());
+    if (rc != ZK_OK) throw Error(rc, rc == ZK_ERR_RANGE ? "poseidon: an input is not below r" : "poseidon: the arity must be 1, 2 or 4");
+    return out;
+}
+// z_0 = 0, z_{k+1} = hash(z_k, z_k): depth + 1 elements
+inline std::vector<FrLocal> zero_hashes(unsigned depth) {
+    std::vector<FrLocal> z{FrLocal(0)};
+    for (unsigned k = 0; k < depth; ++k) z.push_back(hash({z.back(), z.back()}));
+    return z;
+}
+// d_inputs: count x arity elements, d_out: count elements (device pointers, canonical words)
+inline void hash_batch(const Context& c, const void* d_inputs, size_t arity, size_t count, void* d_out) {
+    c.check(zk_poseidon_hash_batch(c.get(), d_inputs, arity, count, d_out), "poseidon::hash_batch");
+}
+}  // namespace poseidon
+
+// zk_poseidon_tree_*: a binary Merkle tree over Poseidon of arity 2 that stays on the device; paths() writes leaf | siblings and the
+// direction bits in the layout Mixgen::run reads as d_in_fields and d_in_bits
+class PoseidonTree {
+   public:
+    PoseidonTree(const Context& c, const void* d_leaves, size_t n_leaves, unsigned depth) : c_(c) {
+        c.check(zk_poseidon_tree_build(c.get(), d_leaves, n_leaves, depth, &t_), "PoseidonTree");
+    }
+    PoseidonTree(const PoseidonTree&) = delete;
+    ~PoseidonTree() { zk_poseidon_tree_free(t_); }
+    FrLocal root() const { FrLocal r; c_.check(zk_poseidon_tree_root(t_, r.w.data()), "PoseidonTree::root"); return r; }
+    size_t n_leaves() const { size_t n = 0; c_.check(zk_poseidon_tree_dims(t_, &n, nullptr), "PoseidonTree::dims"); return n; }
+    unsigned depth() const { unsigned d = 0; c_.check(zk_poseidon_tree_dims(t_, nullptr, &d), "PoseidonTree::dims"); return d; }
+    std::vector<FrLocal> nodes(unsigned level) const {
+        const size_t n = n_leaves();
+        const size_t above = level > 63 ? 0 : (n + (((size_t)1 << level) - 1)) >> level;
+        std::vector<FrLocal> out(level == 0 ? n : above ? above : 1);
+        c_.check(zk_poseidon_tree_nodes(t_, level, out.empty() ? nullptr : out[0].w.data()), "PoseidonTree::nodes");
+        return out;
+    }
+    void paths(const void* d_indices, size_t count, void* d_fields_out, size_t field_stride_words, void* d_bits_out, size_t bits_stride_bytes) const {
+        c_.check(zk_poseidon_tree_paths(t_, d_indices, count, d_fields_out, field_stride_words, d_bits_out, bits_stride_bytes), "PoseidonTree::paths");
+    }
+
+   private:
+    const Context& c_;
+    zk_poseidon_tree* t_ = nullptr;
 };
 
 namespace groth16 {

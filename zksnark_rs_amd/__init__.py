@@ -1037,6 +1037,38 @@ class Context:
         self._check(self.lib.zk_vk_from_crs(self.ptr, crs.ptr, C.byref(p)))
         return VerifyingKey(p, self)
 
+    # ---- Poseidon (zksnark_rs_amd.poseidon) ----
+    def poseidon_hash_batch(self, inputs, arity=None, count=None, d_out_ptr=None):
+        """zk_poseidon_hash_batch.  Device form: inputs = a device pointer to count x arity x 4 canonical words, d_out_ptr = count x 4
+        words.  Host form (arity, count, d_out_ptr left out): inputs (count, arity, 4) uint64 or rows of integers -> (count, 4)
+        uint64, staged through torch tensors on the context's device."""
+        if d_out_ptr is not None:
+            self._check(self.lib.zk_poseidon_hash_batch(self.ptr, C.c_void_p(inputs), arity, count, C.c_void_p(d_out_ptr)))
+            return None
+        import torch
+        a = inputs if isinstance(inputs, np.ndarray) else np.stack([ints_to_limbs(list(row)) for row in inputs])
+        a = np.ascontiguousarray(a, dtype=np.uint64)
+        dev = "cuda:%d" % self.device
+        d_in = torch.from_numpy(a.view(np.int64)).to(dev)
+        d_out = torch.zeros((a.shape[0], 4), dtype=torch.int64, device=dev)
+        torch.cuda.synchronize(dev)
+        self._check(self.lib.zk_poseidon_hash_batch(self.ptr, C.c_void_p(d_in.data_ptr()), a.shape[1], a.shape[0], C.c_void_p(d_out.data_ptr())))
+        return d_out.cpu().numpy().view(np.uint64)
+
+    def poseidon_tree(self, leaves, depth, n_leaves=None):
+        """zk_poseidon_tree_build -> poseidon.PoseidonTree.  leaves: a device pointer to n_leaves x 4 canonical words, or (n_leaves left
+        out) host data, integers or (n, 4) uint64, staged through a torch tensor."""
+        from .poseidon import PoseidonTree
+        if n_leaves is not None:
+            return PoseidonTree(self, leaves, n_leaves, depth)
+        import torch
+        a = leaves if isinstance(leaves, np.ndarray) else ints_to_limbs(list(leaves))
+        a = np.ascontiguousarray(a, dtype=np.uint64).reshape(-1, 4)
+        dev = "cuda:%d" % self.device
+        d = torch.from_numpy(np.ascontiguousarray(np.vstack([a, np.zeros((1, 4), np.uint64)])).view(np.int64)).to(dev)   # never an empty tensor
+        torch.cuda.synchronize(dev)
+        return PoseidonTree(self, d.data_ptr(), a.shape[0], depth)
+
     # ---- profiling ----
     def profile_reset(self):
         self._check(self.lib.zk_profile_reset(self.ptr))

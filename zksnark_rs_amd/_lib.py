@@ -177,6 +177,8 @@ SIGNATURES = {
     "zk_builder_keccak": (C.c_int, [C.c_void_p, u32p, C.c_size_t, C.c_uint, C.c_uint, C.c_uint, u32p, C.c_size_t]),
     "zk_builder_assert_bit": (C.c_int, [C.c_void_p, C.c_uint32]),
     "zk_builder_pack": (C.c_int, [C.c_void_p, u32p, C.c_size_t, u32p]),
+    "zk_builder_poseidon": (C.c_int, [C.c_void_p, u32p, C.c_size_t, u32p]),
+    "zk_builder_merkle_root": (C.c_int, [C.c_void_p, C.c_uint32, u32p, u32p, C.c_size_t, u32p]),
     "zk_builder_finish": (C.c_int, [C.c_void_p, u32p, C.c_size_t, C.POINTER(C.c_void_p)]),
     "zk_circuit_is_boolean": (C.c_int, [C.c_void_p]),
     "zk_circuit_packed_wires": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t)]),
@@ -193,6 +195,15 @@ SIGNATURES = {
     "zk_mixgen_free": (None, [C.c_void_p]),
     "zk_mixgen_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
     "zk_mixgen_eval_fields": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, u32p, C.c_size_t, C.c_void_p]),
+    "zk_poseidon_hash": (C.c_int, [u64p, C.c_size_t, u64p]),
+    "zk_poseidon_params": (C.c_int, [C.c_size_t, C.POINTER(C.c_uint), C.POINTER(C.c_uint), u64p, u64p]),
+    "zk_poseidon_hash_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]),
+    "zk_poseidon_tree_build": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.POINTER(C.c_void_p)]),
+    "zk_poseidon_tree_free": (None, [C.c_void_p]),
+    "zk_poseidon_tree_root": (C.c_int, [C.c_void_p, u64p]),
+    "zk_poseidon_tree_dims": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_uint)]),
+    "zk_poseidon_tree_nodes": (C.c_int, [C.c_void_p, C.c_uint, u64p]),
+    "zk_poseidon_tree_paths": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
     "zk_msm_auto_window": (C.c_int, [C.c_size_t]),
     "zk_msm_auto_window_g2": (C.c_int, [C.c_size_t]),
     "zk_circuit_qap": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),

@@ -317,6 +317,26 @@ class Builder:
         self._check(self.lib.zk_builder_pack(self.ptr, ap, a.size, C.byref(out)))
         return out.value
 
+    def poseidon(self, wires):
+        """-> the wire Poseidon(wires) of 1, 2 or 4 wires (zksnark_rs_amd.poseidon.hash on their values): 217 / 244 / 301 general
+        sub-circuits over linear forms; the output is a field element"""
+        a, ap = self._wires(wires)
+        out = C.c_uint32()
+        self._check(self.lib.zk_builder_poseidon(self.ptr, ap, a.size, C.byref(out)))
+        return out.value
+
+    def merkle_root(self, leaf, siblings, dirs):
+        """-> the root wire of the Merkle path leaf, siblings[k], dirs[k] (1: the path's node is the right child at level k) over
+        Poseidon of arity 2: 246 gates a level, each direction asserted to be a bit.  Inputs created in the order leaf, siblings,
+        dirs (dirs as bit wires) read PoseidonTree.paths' two outputs as Mixgen.run's field and bit inputs."""
+        s, sp = self._wires(siblings)
+        d, dp = self._wires(dirs)
+        if s.size != d.size:
+            raise BuildErr(_lib.ZK_ERR_ARG, "builder: merkle_root takes one direction per sibling")
+        out = C.c_uint32()
+        self._check(self.lib.zk_builder_merkle_root(self.ptr, leaf, sp, dp, s.size, C.byref(out)))
+        return out.value
+
     def pack_bytes(self, wires, bytes_per_element=16):
         """Word8s (or their wires, flat) -> a list of packed wires, bytes_per_element (at most 31) bytes each, little-endian per
         element: a 32-byte digest is [int.from_bytes(d[:16], "little"), int.from_bytes(d[16:], "little")]"""

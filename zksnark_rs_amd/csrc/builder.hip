@@ -1,4 +1,5 @@
-// builder.hip -- zk_builder_*: the C ABI over builder.hpp (host code only; no context, no device).
+// builder.hip -- zk_builder_*: the C ABI over builder.hpp, and zk_poseidon_hash / zk_poseidon_params over poseidon.hpp (host code only;
+// no context, no device).
 #include "builder.hpp"
 
 namespace zk {
@@ -109,6 +110,18 @@ int zk_builder_pack(zk_builder* b, const uint32_t* bits, size_t n_bits, uint32_t
         *out = o.pack(bits, n_bits);
     });
 }
+int zk_builder_poseidon(zk_builder* b, const uint32_t* in_wires, size_t arity, uint32_t* out) {
+    return builder_guard(b, [&](BuilderOps& o) {
+        if (!out || (arity && !in_wires)) BuilderOps::fail("null array");
+        *out = o.poseidon(in_wires, arity);
+    });
+}
+int zk_builder_merkle_root(zk_builder* b, uint32_t leaf, const uint32_t* siblings, const uint32_t* dirs, size_t depth, uint32_t* out) {
+    return builder_guard(b, [&](BuilderOps& o) {
+        if (!out || (depth && (!siblings || !dirs))) BuilderOps::fail("null array");
+        *out = o.merkle_root(leaf, siblings, dirs, depth);
+    });
+}
 int zk_builder_finish(zk_builder* b, const uint32_t* verify_wires, size_t n_verify, zk_circuit** out) {
     if (!out) return ZK_ERR_ARG;
     *out = nullptr;
@@ -116,6 +129,13 @@ int zk_builder_finish(zk_builder* b, const uint32_t* verify_wires, size_t n_veri
         if (n_verify && !verify_wires) BuilderOps::fail("null array");
         *out = builder_finish(o.b, verify_wires, n_verify);
     });
+}
+
+int zk_poseidon_hash(const uint64_t* inputs, size_t arity, uint64_t out[4]) {
+    try { return poseidon_hash_words(inputs, arity, out); } catch (...) { return ZK_ERR_ARG; }
+}
+int zk_poseidon_params(size_t arity, unsigned* rf, unsigned* rp, uint64_t* round_constants, uint64_t* mds) {
+    try { return poseidon_params_words(arity, rf, rp, round_constants, mds); } catch (...) { return ZK_ERR_ARG; }
 }
 
 }  // extern "C"

@@ -12,12 +12,14 @@
 // Every constructor emits exactly the reference's sub-circuits in the reference's order, so gate counts and weights are its own.
 // What differs, on purpose: wires are numbered and ordered deterministically (the reference iterates a HashMap); entries on the
 // constant-zero wire are dropped instead of becoming a witness wire that no constraint pins; its builder -> DummyRep conversion
-// (num_wires empty rows in front) is not reproduced; zk_builder_assert_bit and zk_builder_pack exist.  Header-only and free of device code, so
-// tests/cpp/builder_host.hip compiles it alone under the sanitizers.
+// (num_wires empty rows in front) is not reproduced; zk_builder_assert_bit and zk_builder_pack exist, and so do the Poseidon
+// gadgets (zk_builder_poseidon, zk_builder_merkle_root: general sub-circuits over linear forms, see BuilderOps::Form).  Header-only and
+// free of device code, so tests/cpp/builder_host.hip compiles it alone under the sanitizers.
 #pragma once
 #include <array>
 #include <map>
 #include "circuit.hpp"
+#include "poseidon.hpp"
 
 struct zk_builder {
     struct Term { zk::Fr w; uint32_t wire; };
@@ -100,6 +102,88 @@ struct BuilderOps {
         const uint32_t out = close_sub(l0, r0, true, BOOL_PACK, 0, 0);
         b.kind[out] = 4;
         return out;
+    }
+
+    // ---- Poseidon (poseidon.hpp) as general sub-circuits over linear forms ----
+    // A form is a sum of weighted wires: one term per wire, weights mod r in Montgomery form, no zero weight, the constant carried on
+    // wire 1; the constant-zero wire is the empty form.  Terms are emitted in the order of their wire ids.
+    typedef std::map<uint32_t, Fr> Form;
+    static Form form_of(uint32_t wire) {
+        Form f;
+        if (wire != 0) f[wire] = Fr::one();
+        return f;
+    }
+    static void form_add(Form& a, const Form& x, const Fr& scale) {
+        for (const auto& e : x) {
+            auto it = a.find(e.first);
+            const Fr v = (it == a.end() ? Fr::zero() : it->second) + e.second * scale;
+            if (v.is_zero()) { if (it != a.end()) a.erase(it); }
+            else if (it == a.end()) a.emplace(e.first, v);
+            else it->second = v;
+        }
+    }
+    void push_form(const Form& f) { for (const auto& e : f) b.terms.push_back({e.second, e.first}); }
+    uint32_t sub_forms(const Form& l, const Form& r) {
+        const uint32_t l0 = (uint32_t)b.terms.size();
+        push_form(l);
+        const uint32_t r0 = (uint32_t)b.terms.size();
+        push_form(r);
+        b.boolean = false;
+        return close_sub(l0, r0, true, BOOL_NONE, 0, 0);
+    }
+    // L^5 as L * L = a, a * a = c, c * L = e
+    uint32_t sbox(const Form& f) {
+        const Form a = form_of(sub_forms(f, f));
+        const Form c = form_of(sub_forms(a, a));
+        return sub_forms(c, f);
+    }
+    // The state is t forms.  Round constants and the mix are folded into the forms and cost no gate; an S-box makes its element a
+    // wire again, so in the partial rounds elements 1 .. t-1 grow by one term a round, to t + R_P + 1 at most.  One closing
+    // sub-circuit (state[0]) * 1 = out makes the digest a wire: 3 (R_F t + R_P) + 1 gates.
+    uint32_t poseidon_forms(const Form* in, size_t arity) {
+        const PoseidonParams* p = poseidon_params(arity);
+        if (!p) fail("poseidon: the arity must be 1, 2 or 4, got " + std::to_string(arity));
+        const unsigned t = p->t;
+        Form state[POSEIDON_MAX_T], next[POSEIDON_MAX_T];
+        for (unsigned i = 1; i < t; ++i) state[i] = in[i - 1];
+        const Form unity = form_of(1);
+        for (unsigned rnd = 0; rnd < p->rounds(); ++rnd) {
+            for (unsigned i = 0; i < t; ++i) form_add(state[i], unity, p->c[(size_t)rnd * t + i]);
+            const bool full = rnd < p->rf / 2 || rnd >= p->rf / 2 + p->rp;
+            for (unsigned i = 0; i < (full ? t : 1u); ++i) state[i] = form_of(sbox(state[i]));
+            for (unsigned i = 0; i < t; ++i) {
+                next[i].clear();
+                for (unsigned j = 0; j < t; ++j) form_add(next[i], state[j], p->m[i * t + j]);
+            }
+            for (unsigned i = 0; i < t; ++i) state[i].swap(next[i]);
+        }
+        return sub_forms(state[0], unity);
+    }
+    uint32_t poseidon(const uint32_t* in, size_t arity) {
+        if (!poseidon_rp(arity)) fail("poseidon: the arity must be 1, 2 or 4, got " + std::to_string(arity));
+        Form f[POSEIDON_MAX_T - 1];
+        for (size_t i = 0; i < arity; ++i) { known(in[i]); f[i] = form_of(in[i]); }
+        return poseidon_forms(f, arity);
+    }
+    // per level: dir is a bit; d = dir * (sib - cur); the next cur = Poseidon(cur + d, sib - d), the pair in the order the bit says
+    uint32_t merkle_root(uint32_t leaf, const uint32_t* siblings, const uint32_t* dirs, size_t depth) {
+        known(leaf);
+        for (size_t k = 0; k < depth; ++k) { known(siblings[k]); known(dirs[k]); }
+        const Fr one = Fr::one(), minus = -Fr::one();
+        uint32_t cur = leaf;
+        for (size_t k = 0; k < depth; ++k) {
+            assert_bit(dirs[k]);
+            Form diff = form_of(siblings[k]);
+            form_add(diff, form_of(cur), minus);
+            Form dir;
+            dir[dirs[k]] = one;                 // an entry on the constant-zero wire is dropped at finish, like everywhere
+            const Form d = form_of(sub_forms(dir, diff));
+            Form pair[2] = {form_of(cur), form_of(siblings[k])};
+            form_add(pair[0], d, one);
+            form_add(pair[1], d, minus);
+            cur = poseidon_forms(pair, 2);
+        }
+        return cur;
     }
 
     // ---- mod.rs:723-798, 939-950 ----
