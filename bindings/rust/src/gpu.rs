@@ -220,6 +220,8 @@ extern "C" {
     fn zk_poseidon_tree_nodes(t: *const ZkPoseidonTree, level: c_uint, out: *mut u64) -> c_int;
     fn zk_poseidon_tree_paths(t: *mut ZkPoseidonTree, d_indices: *const c_void, count: usize, d_fields_out: *mut c_void, field_stride_words: usize,
                               d_bits_out: *mut c_void, bits_stride_bytes: usize) -> c_int;
+    fn zk_poseidon_tree_update(t: *mut ZkPoseidonTree, d_indices: *const c_void, d_values: *const c_void, count: usize) -> c_int;
+    fn zk_poseidon_tree_append(t: *mut ZkPoseidonTree, d_leaves: *const c_void, count: usize) -> c_int;
     fn zk_boolgen_create(ctx: *mut ZkCtx, c: *const ZkCircuit, out: *mut *mut ZkBoolgen) -> c_int;
     fn zk_boolgen_free(g: *mut ZkBoolgen);
     fn zk_boolgen_run(g: *mut ZkBoolgen, d_in_bits: *const c_void, in_stride_bytes: usize, count: usize, d_weights_out: *mut c_void,
@@ -1495,6 +1497,15 @@ impl PoseidonTree {
     pub fn paths(&self, d_indices: *const c_void, count: usize, d_fields_out: *mut c_void, field_stride_words: usize, d_bits_out: *mut c_void,
                  bits_stride_bytes: usize) {
         unsafe { check(self.ctx, zk_poseidon_tree_paths(self.t, d_indices, count, d_fields_out, field_stride_words, d_bits_out, bits_stride_bytes)) }
+    }
+    /// leaf d_indices[j] = d_values[j] (count u64 indices, count x 4 canonical words, on the device) and every node above, up to the
+    /// root; an index >= n_leaves, a value >= r or an index that occurs twice is refused and leaves the tree as it was
+    pub fn update(&mut self, d_indices: *const c_void, d_values: *const c_void, count: usize) {
+        unsafe { check(self.ctx, zk_poseidon_tree_update(self.t, d_indices, d_values, count)) }
+    }
+    /// `count` more leaves (count x 4 canonical words on the device) behind the last one; dims() reports the new size
+    pub fn append(&mut self, d_leaves: *const c_void, count: usize) {
+        unsafe { check(self.ctx, zk_poseidon_tree_append(self.t, d_leaves, count)) }
     }
 }
 

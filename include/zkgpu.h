@@ -532,12 +532,12 @@ int zk_poseidon_hash_batch(zk_ctx* ctx, const void* d_inputs, size_t arity, size
  * z_{k+1} = hash(z_k, z_k) -- so a tree of depth 20 over 1000 leaves stores about 2000 nodes, not 2^21, and n_leaves == 0 gives
  * root = z_depth.  d_leaves: n_leaves x 4 canonical words on the device (copied; may be NULL when n_leaves == 0).  One kernel launch
  * per level; complete on return.  The context must outlive the tree.  ZK_ERR_ARG with text: depth > 32, n_leaves > 2^depth, a null
- * pointer.  ZK_ERR_RANGE with text naming the lowest such leaf: a leaf >= r.  *out is NULL on every failure.  A built tree is not
- * updated or appended to. */
+ * pointer.  ZK_ERR_RANGE with text naming the lowest such leaf: a leaf >= r.  *out is NULL on every failure.  The tree changes
+ * through zk_poseidon_tree_update and zk_poseidon_tree_append below; n_leaves == 0 followed by appends starts a tree that grows. */
 typedef struct zk_poseidon_tree zk_poseidon_tree;
 int zk_poseidon_tree_build(zk_ctx* ctx, const void* d_leaves, size_t n_leaves, unsigned depth, zk_poseidon_tree** out);
 void zk_poseidon_tree_free(zk_poseidon_tree* t);     /* NULL is a no-op */
-/* the root, 4 canonical words (kept on the host by zk_poseidon_tree_build) */
+/* the root, 4 canonical words (kept on the host by zk_poseidon_tree_build, _update and _append) */
 int zk_poseidon_tree_root(const zk_poseidon_tree* t, uint64_t out[4]);
 /* either pointer may be NULL */
 int zk_poseidon_tree_dims(const zk_poseidon_tree* t, size_t* n_leaves, unsigned* depth);
@@ -555,6 +555,24 @@ int zk_poseidon_tree_nodes(const zk_poseidon_tree* t, unsigned level, uint64_t* 
  * pointer.  ZK_ERR_RANGE with text naming the lowest such instance: an index >= n_leaves; the outputs are then unspecified. */
 int zk_poseidon_tree_paths(zk_poseidon_tree* t, const void* d_indices, size_t count, void* d_fields_out, size_t field_stride_words,
                            void* d_bits_out, size_t bits_stride_bytes);
+/* Sets leaf indices[j] = values[j] for j < count and rehashes every node with a changed leaf under it, up to the root; afterwards the
+ * root, every level and every path are what zk_poseidon_tree_build over the edited leaves gives, word for word.  d_indices: count
+ * uint64 leaf indices, d_values: count x 4 canonical words, both on the device, 8-byte aligned.  One checking kernel, one scatter and
+ * one launch per level over the list of that level's changed nodes, each parent hashed once; on the context's stream, complete on
+ * return (the root on the host is refreshed).  count == 0: ZK_OK, nothing touched.  Every refusal is found before anything is written and leaves the tree
+ * as it was; where several hold, the first of: ZK_ERR_ARG: a null or misaligned pointer.  ZK_ERR_RANGE with text naming the lowest
+ * such instance j: an index >= n_leaves.  ZK_ERR_RANGE with text naming the lowest such instance j: a value >= r.  ZK_ERR_ARG with
+ * text naming the lowest such LEAF: an index that occurs more than once in the call, equal values or not -- there is no
+ * last-wins rule. */
+int zk_poseidon_tree_update(zk_poseidon_tree* t, const void* d_indices, const void* d_values, size_t count);
+/* Appends `count` leaves, which become leaves n_leaves .. n_leaves + count - 1; zk_poseidon_tree_dims reports the new size and the
+ * tree is what zk_poseidon_tree_build over all the leaves gives.  d_leaves: count x 4 canonical words on the device, 8-byte aligned
+ * (copied).  The node buffer has a capacity that at least doubles when an append exceeds it (the levels are copied device to
+ * device), so a run of small appends copies a linear total.  One checking kernel and one launch per level over the nodes above the
+ * new leaves; complete on return.  count == 0: ZK_OK.  Every refusal leaves the tree as it was: ZK_ERR_ARG with text:
+ * n_leaves + count > 2^depth, a null or misaligned pointer.  ZK_ERR_RANGE with text naming the lowest such position in d_leaves: a
+ * leaf >= r. */
+int zk_poseidon_tree_append(zk_poseidon_tree* t, const void* d_leaves, size_t count);
 
 /* ------------------------------------------------------------------------------------------
  * CRS  (SigmaG1 / SigmaG2, groth16/mod.rs:105-121)

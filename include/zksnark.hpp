@@ -505,6 +505,13 @@ class PoseidonTree {
     void paths(const void* d_indices, size_t count, void* d_fields_out, size_t field_stride_words, void* d_bits_out, size_t bits_stride_bytes) const {
         c_.check(zk_poseidon_tree_paths(t_, d_indices, count, d_fields_out, field_stride_words, d_bits_out, bits_stride_bytes), "PoseidonTree::paths");
     }
+    // leaf d_indices[j] = d_values[j] (count uint64 indices, count x 4 canonical words, on the device) and every node above, up to the
+    // root; an index >= n_leaves, a value >= r or an index that occurs twice is refused and leaves the tree as it was
+    void update(const void* d_indices, const void* d_values, size_t count) {
+        c_.check(zk_poseidon_tree_update(t_, d_indices, d_values, count), "PoseidonTree::update");
+    }
+    // `count` more leaves (count x 4 canonical words on the device) behind the last one; n_leaves() follows
+    void append(const void* d_leaves, size_t count) { c_.check(zk_poseidon_tree_append(t_, d_leaves, count), "PoseidonTree::append"); }
 
    private:
     const Context& c_;

@@ -204,6 +204,8 @@ SIGNATURES = {
     "zk_poseidon_tree_dims": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_uint)]),
     "zk_poseidon_tree_nodes": (C.c_int, [C.c_void_p, C.c_uint, u64p]),
     "zk_poseidon_tree_paths": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
+    "zk_poseidon_tree_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "zk_poseidon_tree_append": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "zk_msm_auto_window": (C.c_int, [C.c_size_t]),
     "zk_msm_auto_window_g2": (C.c_int, [C.c_size_t]),
     "zk_circuit_qap": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),

@@ -4,7 +4,8 @@ R_P = 56 / 57 / 60 -- circomlib's parameter sets, generated in code from the Gra
     hash(ints), params(arity), zero_hashes(depth)      host code, no context (zk_poseidon_hash, zk_poseidon_params)
     Context.poseidon_hash_batch(...)                   one hash per lane on the GPU (zk_poseidon_hash_batch)
     Context.poseidon_tree(leaves, depth) -> PoseidonTree    a binary Merkle tree that stays on the device; .paths() hands out
-                                                       authentication paths in the layout Mixgen.run reads
+                                                       authentication paths in the layout Mixgen.run reads; .update() and
+                                                       .append() change it in place (zk_poseidon_tree_update / _append)
     circuit.Builder.poseidon / .merkle_root            the same function as sub-circuits
 """
 import ctypes as C
@@ -56,7 +57,9 @@ def zero_hashes(depth):
 class PoseidonTree:
     """zk_poseidon_tree: a binary Merkle tree over Poseidon of arity 2, resident on the device.  Level 0 is the leaves, level k holds
     ceil(n_leaves / 2^k) nodes (at least one from level 1 up); a child that does not exist counts as zero_hashes(depth)[k].  The
-    context must stay open.  Not updated after it is built."""
+    context must stay open.  update() rewrites leaves and append() adds leaves behind the last one; both rehash only the nodes above
+    the changed leaves and leave the tree as zk_poseidon_tree_build over the new leaf list would make it.  n_leaves follows the
+    library (zk_poseidon_tree_dims) after every accepted call; a refused call changes nothing."""
 
     def __init__(self, ctx, d_leaves_ptr, n_leaves, depth):
         self.ctx, self.lib = ctx, ctx.lib
@@ -112,3 +115,47 @@ class PoseidonTree:
         torch.cuda.synchronize(dev)
         self.paths_dev(d_idx.data_ptr(), idx.size, d_fields.data_ptr(), d_bits.data_ptr(), bits_stride_bytes=max(self.bit_bytes, 1))
         return d_fields.cpu().numpy().view(np.uint64)[:idx.size], d_bits.cpu().numpy()[:idx.size, :self.bit_bytes]
+
+    def _refresh_dims(self):
+        n = C.c_size_t()
+        self.ctx._check(self.lib.zk_poseidon_tree_dims(self.ptr, C.byref(n), None))
+        self.n_leaves = n.value
+
+    def update_dev(self, d_indices_ptr, d_values_ptr, count):
+        """device to device: leaf indices[j] = values[j] for count uint64 indices and count x 4 canonical words.  ZkError, and the tree
+        as it was: an index >= n_leaves or a value >= r (ZK_ERR_RANGE, naming the lowest instance), an index that occurs twice
+        (ZK_ERR_ARG, naming the lowest such leaf)"""
+        self.ctx._check(self.lib.zk_poseidon_tree_update(self.ptr, C.c_void_p(d_indices_ptr), C.c_void_p(d_values_ptr), count))
+        self._refresh_dims()
+
+    def update(self, indices, values):
+        """host indices and values (integers or (count, 4) uint64), staged through torch tensors"""
+        import torch
+        idx = np.ascontiguousarray(np.asarray(list(indices), dtype=np.uint64))
+        dev = "cuda:%d" % self.ctx.device
+        d_idx = torch.from_numpy(np.append(idx, np.uint64(0)).view(np.int64)).to(dev)     # never an empty tensor
+        d_val = self._stage(values, dev)
+        if d_val.shape[0] - 1 != idx.size:
+            raise ZkError(_lib.ZK_ERR_ARG, "poseidon tree: %d indices and %d values" % (idx.size, d_val.shape[0] - 1))
+        self.update_dev(d_idx.data_ptr(), d_val.data_ptr(), idx.size)
+
+    def append_dev(self, d_leaves_ptr, count):
+        """device to device: count x 4 canonical words become leaves n_leaves .. n_leaves + count - 1.  ZkError, and the tree as it
+        was: more leaves than 2^depth (ZK_ERR_ARG), a leaf >= r (ZK_ERR_RANGE, naming the lowest position)"""
+        self.ctx._check(self.lib.zk_poseidon_tree_append(self.ptr, C.c_void_p(d_leaves_ptr), count))
+        self._refresh_dims()
+
+    def append(self, leaves):
+        """host leaves (integers or (count, 4) uint64), staged through a torch tensor"""
+        d = self._stage(leaves, "cuda:%d" % self.ctx.device)
+        self.append_dev(d.data_ptr(), d.shape[0] - 1)
+
+    @staticmethod
+    def _stage(values, dev):
+        """-> a device tensor of the values' limbs and one row of zeros behind them (never an empty tensor)"""
+        import torch
+        a = values if isinstance(values, np.ndarray) else ints_to_limbs(list(values))
+        a = np.ascontiguousarray(a, dtype=np.uint64).reshape(-1, 4)
+        d = torch.from_numpy(np.ascontiguousarray(np.vstack([a, np.zeros((1, 4), np.uint64)])).view(np.int64)).to(dev)
+        torch.cuda.synchronize(dev)
+        return d
