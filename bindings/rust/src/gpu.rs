@@ -209,6 +209,18 @@ extern "C" {
                      d_weights_out: *mut c_void, m: usize) -> c_int;
     fn zk_mixgen_eval_fields(g: *mut ZkMixgen, d_in_bits: *const c_void, in_stride_bytes: usize, d_in_fields: *const c_void, count: usize,
                              wires: *const u32, n_wires: usize, d_out_words: *mut c_void) -> c_int;
+    // Baby Jubjub over Fr: builder gadgets, host arithmetic, GPU batch scalar multiplication
+    fn zk_builder_babyjub_assert_on_curve(b: *mut ZkBuilder, xy: *const u32) -> c_int;
+    fn zk_builder_babyjub_add(b: *mut ZkBuilder, p: *const u32, q: *const u32, out: *mut u32) -> c_int;
+    fn zk_builder_babyjub_mul_fixed(b: *mut ZkBuilder, bits: *const u32, n_bits: usize, out: *mut u32) -> c_int;
+    fn zk_builder_babyjub_mul(b: *mut ZkBuilder, p_xy: *const u32, bits: *const u32, n_bits: usize, out: *mut u32) -> c_int;
+    fn zk_builder_babyjub_affine(b: *mut ZkBuilder, p: *const u32, xy: *const u32) -> c_int;
+    fn zk_babyjub_params(a: *mut u64, d: *mut u64, order: *mut u64, base8: *mut u64, generator: *mut u64) -> c_int;
+    fn zk_babyjub_on_curve(p: *const u64) -> c_int;
+    fn zk_babyjub_add(p: *const u64, q: *const u64, out: *mut u64) -> c_int;
+    fn zk_babyjub_mul(scalar: *const u64, p: *const u64, out: *mut u64) -> c_int;
+    fn zk_babyjub_mul_batch(ctx: *mut ZkCtx, d_scalars: *const c_void, d_points: *const c_void, count: usize, d_out: *mut c_void,
+                            out_stride_words: usize) -> c_int;
     // Poseidon over Fr (circomlib's parameter sets): host hash, GPU batch hashing, a device-resident Merkle tree and its paths
     fn zk_poseidon_hash(inputs: *const u64, arity: usize, out: *mut u64) -> c_int;
     fn zk_poseidon_params(arity: usize, rf: *mut c_uint, rp: *mut c_uint, round_constants: *mut u64, mds: *mut u64) -> c_int;
@@ -1316,6 +1328,28 @@ impl GpuCircuitBuilder {
         self.ok(unsafe { zk_builder_merkle_root(self.0, leaf, siblings.as_ptr(), dirs.as_ptr(), dirs.len(), &mut out) });
         out
     }
+    /// Baby Jubjub: a point is three wires [X, Y, Z], projective; an affine point is [x, y, 1].  The curve equation on (x, y): 4 gates
+    pub fn babyjub_assert_on_curve(&mut self, xy: [WireId; 2]) { self.ok(unsafe { zk_builder_babyjub_assert_on_curve(self.0, xy.as_ptr()) }) }
+    /// p + q for all pairs of curve points: 11 gates, 10 when q[2] is the unity wire; the operands are not asserted on the curve
+    pub fn babyjub_add(&mut self, p: [WireId; 3], q: [WireId; 3]) -> [WireId; 3] {
+        let mut out = [0u32; 3];
+        self.ok(unsafe { zk_builder_babyjub_add(self.0, p.as_ptr(), q.as_ptr(), out.as_mut_ptr()) });
+        out
+    }
+    /// [sum 2^i bits[i]] Base8 over 1..256 bit wires, each asserted: 1414 gates for 251 bits
+    pub fn babyjub_mul_fixed(&mut self, bits: &[WireId]) -> [WireId; 3] {
+        let mut out = [0u32; 3];
+        self.ok(unsafe { zk_builder_babyjub_mul_fixed(self.0, bits.as_ptr(), bits.len(), out.as_mut_ptr()) });
+        out
+    }
+    /// [sum 2^i bits[i]] P for the affine wires p_xy, asserted on the curve: 4 + n + 2 + 19 (n - 1) gates
+    pub fn babyjub_mul(&mut self, p_xy: [WireId; 2], bits: &[WireId]) -> [WireId; 3] {
+        let mut out = [0u32; 3];
+        self.ok(unsafe { zk_builder_babyjub_mul(self.0, p_xy.as_ptr(), bits.as_ptr(), bits.len(), out.as_mut_ptr()) });
+        out
+    }
+    /// pins the existing wires xy as the affine form of p: 4 gates
+    pub fn babyjub_affine(&mut self, p: [WireId; 3], xy: [WireId; 2]) { self.ok(unsafe { zk_builder_babyjub_affine(self.0, p.as_ptr(), xy.as_ptr()) }) }
     pub fn fan_in(&mut self, inputs: &[WireId], g: Gate) -> WireId {
         let mut out = 0u32;
         self.ok(unsafe { zk_builder_fan_in(self.0, g as c_int, inputs.as_ptr(), inputs.len(), &mut out) });
@@ -1464,6 +1498,31 @@ pub fn poseidon_hash(inputs: &[[u64; 4]]) -> Option<[u64; 4]> {
 /// zk_poseidon_hash_batch: `count` hashes of `arity` elements each, device to device
 pub fn poseidon_hash_batch(ctx: *mut ZkCtx, d_inputs: *const c_void, arity: usize, count: usize, d_out: *mut c_void) {
     unsafe { check(ctx, zk_poseidon_hash_batch(ctx, d_inputs, arity, count, d_out)) }
+}
+
+/// Baby Jubjub over Fr: a point is [x words | y words], 8 canonical words.  None: a coordinate >= r or a point off the curve
+pub fn babyjub_on_curve(p: &[u64; 8]) -> Option<bool> {
+    match unsafe { zk_babyjub_on_curve(p.as_ptr()) } { 1 => Some(true), 0 => Some(false), _ => None }
+}
+pub fn babyjub_add(p: &[u64; 8], q: &[u64; 8]) -> Option<[u64; 8]> {
+    let mut out = [0u64; 8];
+    if unsafe { zk_babyjub_add(p.as_ptr(), q.as_ptr(), out.as_mut_ptr()) } == 0 { Some(out) } else { None }
+}
+/// [scalar] p, the scalar an integer of 256 bits that is not reduced; p None: Base8
+pub fn babyjub_mul(scalar: &[u64; 4], p: Option<&[u64; 8]>) -> Option<[u64; 8]> {
+    let mut out = [0u64; 8];
+    let pp = p.map_or(std::ptr::null(), |x| x.as_ptr());
+    if unsafe { zk_babyjub_mul(scalar.as_ptr(), pp, out.as_mut_ptr()) } == 0 { Some(out) } else { None }
+}
+/// (a, d, order of Base8, Base8, Generator)
+pub fn babyjub_params() -> ([u64; 4], [u64; 4], [u64; 4], [u64; 8], [u64; 8]) {
+    let (mut a, mut d, mut l, mut b, mut g) = ([0u64; 4], [0u64; 4], [0u64; 4], [0u64; 8], [0u64; 8]);
+    unsafe { zk_babyjub_params(a.as_mut_ptr(), d.as_mut_ptr(), l.as_mut_ptr(), b.as_mut_ptr(), g.as_mut_ptr()) };
+    (a, d, l, b, g)
+}
+/// zk_babyjub_mul_batch: `count` scalar multiplications, device to device; d_points null: Base8; out_stride_words 0: packed
+pub fn babyjub_mul_batch(ctx: *mut ZkCtx, d_scalars: *const c_void, d_points: *const c_void, count: usize, d_out: *mut c_void, out_stride_words: usize) {
+    unsafe { check(ctx, zk_babyjub_mul_batch(ctx, d_scalars, d_points, count, d_out, out_stride_words)) }
 }
 
 /// zk_poseidon_tree_*: a binary Merkle tree over Poseidon of arity 2 that stays on the device; paths() writes leaf | siblings and the

@@ -411,6 +411,32 @@ int zk_builder_poseidon(zk_builder* b, const uint32_t* in_wires, size_t arity, u
  * out.  Per level: zk_builder_assert_bit(dir), one gate dir * (sib - cur) = d, and Poseidon of the forms (cur + d, sib - d) -- 246
  * gates.  depth == 0: *out = leaf, nothing is emitted.  ZK_ERR_ARG with text: an unknown wire, a null array. */
 int zk_builder_merkle_root(zk_builder* b, uint32_t leaf, const uint32_t* siblings, const uint32_t* dirs, size_t depth, uint32_t* out);
+/* Baby Jubjub gadgets (see "Baby Jubjub" below).  A point is THREE wires (X, Y, Z), projective: x = X / Z, y = Y / Z; an affine point
+ * is (x, y, ZK_WIRE_ONE).  The tape cannot divide, so the gadgets evaluate the projective formulas forward and never return affine
+ * wires; where a statement needs affine coordinates the caller supplies them as wires (typically ZK_WIRE_FIELD inputs computed by
+ * zk_babyjub_mul or zk_babyjub_mul_batch) and zk_builder_babyjub_affine pins them.  The Z of every gadget's result is a product of the
+ * addition law's denominators, which do not vanish on curve points, so x Z = X determines x.  All gates are general sub-circuits over
+ * linear forms (field-class, as zk_builder_poseidon).  ZK_ERR_ARG with text: an unknown wire, a null array, n_bits outside 1..256; a
+ * refused call emits nothing.  Output arrays may alias input arrays.
+ * The gates x x = u, y y = v, u v = w and the assertion (a u + v - 1 - d w) * 1 = 0 without output: 4 gates. */
+int zk_builder_babyjub_assert_on_curve(zk_builder* b, const uint32_t xy[2]);
+/* out = p + q by add-2008-bbjlp: Z1 Z2 = A, A A = B, X1 X2 = C, Y1 Y2 = D, C D = E, (X1 + Y1)(X2 + Y2) = H, A (B - d E), A (B + d E),
+ * then X3, Y3, Z3: 11 gates, 10 when q[2] is ZK_WIRE_ONE (A = Z1 is then no gate).  The law is complete: the result is right for ALL
+ * pairs of curve points, equal, opposite and of low order included.  It does NOT assert that p or q lie on the curve. */
+int zk_builder_babyjub_add(zk_builder* b, const uint32_t p[3], const uint32_t q[3], uint32_t out[3]);
+/* out = [sum_i 2^i bits[i]] Base8, 1 <= n_bits <= 256.  zk_builder_assert_bit on every bit first; then windows of 3 bits from the least
+ * significant: the window's point j 8^k Base8 (j = 0: the identity) as two forms, multilinear in the bits, over the 4 product gates
+ * b0 b1, b0 b2, b1 b2, (b0 b1) b2 (a last window of two bits: 1, of one bit: 0); the first window is the accumulator, every further
+ * one costs a mixed addition of 10 gates.  n_bits <= 3: two closing gates (form) * 1 make X and Y wires and out[2] = ZK_WIRE_ONE.
+ * Gates: n_bits + 4 floor(n_bits / 3) + [n_bits mod 3 = 2] + 10 (windows - 1), or + 2 for one window: 1414 for 251 bits, 1446 for 256. */
+int zk_builder_babyjub_mul_fixed(zk_builder* b, const uint32_t* bits, size_t n_bits, uint32_t out[3]);
+/* out = [sum_i 2^i bits[i]] P for the affine point P = (p_xy[0], p_xy[1]), 1 <= n_bits <= 256.  zk_builder_babyjub_assert_on_curve(P)
+ * and zk_builder_assert_bit on every bit first; then from the most significant bit: the selection b Px, b (Py - 1) of P or the identity
+ * (2 gates), and per further bit a doubling (7 gates), the selection and a mixed addition (10).  Gates: 4 + n_bits + 2 + 19 (n_bits - 1);
+ * n_bits = 1: one closing gate makes Y a wire (8 gates) and out[2] = ZK_WIRE_ONE. */
+int zk_builder_babyjub_mul(zk_builder* b, const uint32_t p_xy[2], const uint32_t* bits, size_t n_bits, uint32_t out[3]);
+/* Pins the existing wires xy as the affine form of p: x Z = t, (t - X) * 1 = 0, and the same for y: 4 gates, no new point. */
+int zk_builder_babyjub_affine(zk_builder* b, const uint32_t p[3], const uint32_t xy[2]);
 /* The circuit as an ordinary zk_circuit (free it with zk_circuit_free; the builder may be freed before or after).  Witness order: the
  * constant 1, the verify wires in the order given (qap.input = n_verify), the remaining input wires in creation order, the remaining
  * wires by id.  Sub-circuit k is gate k (0-based), at root k + 1 of zk_circuit_qap / _qap_sparse.  ZK_ERR_ARG with text: a verify wire
@@ -573,6 +599,36 @@ int zk_poseidon_tree_update(zk_poseidon_tree* t, const void* d_indices, const vo
  * n_leaves + count > 2^depth, a null or misaligned pointer.  ZK_ERR_RANGE with text naming the lowest such position in d_leaves: a
  * leaf >= r. */
 int zk_poseidon_tree_append(zk_poseidon_tree* t, const void* d_leaves, size_t count);
+
+/* ------------------------------------------------------------------------------------------
+ * Baby Jubjub (csrc/babyjub.hpp, csrc/babyjub.hip): the twisted Edwards curve a x^2 + y^2 = 1 + d x^2 y^2 over the BN254 scalar field
+ * with a = 168700, d = 168696 -- circomlib's, iden3's and Semaphore's curve.  The identity is (0, 1); Base8 generates the subgroup of
+ * prime order l (251 bits), Generator the whole group of order 8 l, Base8 = 8 Generator.  a is a square and d is not, so the addition
+ * law is complete and no point is a special case.  A point is 8 canonical words, x then y.  Refusals: a coordinate >= r is
+ * ZK_ERR_RANGE, and so is a point off the curve -- the status zk_crs_upload gives a CRS point off its curve; the range check comes first.
+ * ---------------------------------------------------------------------------------------- */
+/* a, d, the order l of Base8, Base8 and Generator as canonical words.  Any pointer may be NULL.  Always ZK_OK. */
+int zk_babyjub_params(uint64_t a[4], uint64_t d[4], uint64_t order[4], uint64_t base8[8], uint64_t generator[8]);
+/* 1: p is on the curve, 0: it is not.  ZK_ERR_ARG: a null pointer.  ZK_ERR_RANGE: a coordinate >= r. */
+int zk_babyjub_on_curve(const uint64_t p[8]);
+/* out = p + q on the host, no context; out may alias p or q.  ZK_ERR_ARG: a null pointer.  ZK_ERR_RANGE: see above. */
+int zk_babyjub_add(const uint64_t p[8], const uint64_t q[8], uint64_t out[8]);
+/* out = [scalar] p on the host, no context; p == NULL means Base8.  The scalar is an integer of 256 bits, taken as an integer and NOT
+ * reduced (points outside the subgroup of order l see the difference).  ZK_ERR_ARG: scalar or out null.  ZK_ERR_RANGE: see above. */
+int zk_babyjub_mul(const uint64_t scalar[4], const uint64_t* p, uint64_t out[8]);
+/* `count` scalar multiplications on the GPU, one per lane: instance j computes [scalars[j]] points[j], or [scalars[j]] Base8 where
+ * d_points is NULL.  d_scalars: count x 4 words, any 256-bit integers; d_points: count x 8 canonical words; the result, affine and
+ * canonical (x, y), goes to the 8 words at d_out + j * out_stride_words (words of 64 bits) and nothing else is written.
+ * out_stride_words 0 or 8: packed, which is d_inputs of zk_poseidon_hash_batch(ctx, d_out, 2, count, ...); a larger stride lands a
+ * result inside a row of zk_mixgen_run's d_in_fields.  All device pointers, 8-byte aligned.  Complete on return.  count == 0: ZK_OK,
+ * nothing touched.  Fixed base: additions only, over a table of j 16^k Base8 (ZK_BABYJUB_FIXED_WINDOW bits a window) uploaded once
+ * per context.  Variable base: windows of ZK_BABYJUB_VAR_WINDOW bits over P, 2 P, 3 P in registers.  Both kernels run the same
+ * instruction stream in every lane whatever the scalars and points.  ZK_ERR_ARG with text: a null or misaligned pointer, a stride in
+ * 1..7.  Variable base only, found on the device BEFORE anything is written, d_out untouched, the text naming the LOWEST such
+ * instance: a coordinate >= r (ZK_ERR_RANGE); if there is none, a point off the curve (ZK_ERR_RANGE). */
+#define ZK_BABYJUB_FIXED_WINDOW 4
+#define ZK_BABYJUB_VAR_WINDOW 2
+int zk_babyjub_mul_batch(zk_ctx* ctx, const void* d_scalars, const void* d_points, size_t count, void* d_out, size_t out_stride_words);
 
 /* ------------------------------------------------------------------------------------------
  * CRS  (SigmaG1 / SigmaG2, groth16/mod.rs:105-121)

@@ -346,6 +346,26 @@ class Circuit {
         return o;
     }
 
+    // Baby Jubjub (babyjub::): a point is three wires (X, Y, Z), projective; an affine point is (x, y, ZK_WIRE_ONE)
+    typedef std::array<WireId, 3> Point;
+    // a x^2 + y^2 = 1 + d x^2 y^2 on the wires (x, y): 4 gates, the last one an assertion without output
+    void babyjub_assert_on_curve(WireId x, WireId y) { const WireId xy[2] = {x, y}; check(zk_builder_babyjub_assert_on_curve(b_, xy)); }
+    // p + q, right for all pairs of curve points: 11 gates, 10 when q's Z is ZK_WIRE_ONE; the operands are not asserted on the curve
+    Point babyjub_add(const Point& p, const Point& q) { Point o; check(zk_builder_babyjub_add(b_, p.data(), q.data(), o.data())); return o; }
+    // [sum 2^i bits[i]] Base8 over 1..256 bit wires, each asserted: 1414 gates for 251 bits
+    template <class Wires>
+    Point babyjub_mul_fixed(const Wires& bits) { Point o; check(zk_builder_babyjub_mul_fixed(b_, bits.data(), bits.size(), o.data())); return o; }
+    // [sum 2^i bits[i]] P for the affine wires (px, py), asserted on the curve: 4 + n + 2 + 19 (n - 1) gates
+    template <class Wires>
+    Point babyjub_mul(WireId px, WireId py, const Wires& bits) {
+        const WireId xy[2] = {px, py};
+        Point o;
+        check(zk_builder_babyjub_mul(b_, xy, bits.data(), bits.size(), o.data()));
+        return o;
+    }
+    // pins the existing wires (x, y) as the affine form of p: 4 gates
+    void babyjub_affine(const Point& p, WireId x, WireId y) { const WireId xy[2] = {x, y}; check(zk_builder_babyjub_affine(b_, p.data(), xy)); }
+
     template <class Wires>
     WireId fan_in(const Wires& inputs, Gate g) { WireId o; check(zk_builder_fan_in(b_, (int)g, inputs.data(), inputs.size(), &o)); return o; }
     template <class Wires>
@@ -482,6 +502,57 @@ inline void hash_batch(const Context& c, const void* d_inputs, size_t arity, siz
     c.check(zk_poseidon_hash_batch(c.get(), d_inputs, arity, count, d_out), "poseidon::hash_batch");
 }
 }  // namespace poseidon
+
+// Baby Jubjub over Fr (zk_babyjub_*): a x^2 + y^2 = 1 + d x^2 y^2, a = 168700, d = 168696; the identity is (0, 1).  A coordinate >= r
+// and a point off the curve both throw Error(ZK_ERR_RANGE).
+namespace babyjub {
+struct Point {
+    FrLocal x, y;
+    bool operator==(const Point& o) const { return x.w == o.x.w && y.w == o.y.w; }
+};
+struct Params { FrLocal a, d, order; Point base8, generator; };
+namespace detail {
+inline void words(const Point& p, uint64_t w[8]) { std::copy(p.x.w.begin(), p.x.w.end(), w); std::copy(p.y.w.begin(), p.y.w.end(), w + 4); }
+inline Point point(const uint64_t w[8]) { Point p; std::copy(w, w + 4, p.x.w.begin()); std::copy(w + 4, w + 8, p.y.w.begin()); return p; }
+inline void check(int rc) {
+    if (rc < 0) throw Error(rc, rc == ZK_ERR_RANGE ? "babyjub: a coordinate is not below r, or the point is not on the curve" : "babyjub: bad argument");
+}
+}  // namespace detail
+inline Params params() {
+    Params p;
+    uint64_t b[8], g[8];
+    detail::check(zk_babyjub_params(p.a.w.data(), p.d.w.data(), p.order.w.data(), b, g));
+    p.base8 = detail::point(b);
+    p.generator = detail::point(g);
+    return p;
+}
+inline bool on_curve(const Point& p) {
+    uint64_t w[8];
+    detail::words(p, w);
+    const int rc = zk_babyjub_on_curve(w);
+    detail::check(rc);
+    return rc == 1;
+}
+inline Point add(const Point& p, const Point& q) {
+    uint64_t a[8], b[8], o[8];
+    detail::words(p, a);
+    detail::words(q, b);
+    detail::check(zk_babyjub_add(a, b, o));
+    return detail::point(o);
+}
+// [scalar] p; the scalar is four words of 64 bits, least significant first, taken as an integer; p == nullptr: Base8
+inline Point mul(const std::array<uint64_t, 4>& scalar, const Point* p = nullptr) {
+    uint64_t a[8], o[8];
+    if (p) detail::words(*p, a);
+    detail::check(zk_babyjub_mul(scalar.data(), p ? a : nullptr, o));
+    return detail::point(o);
+}
+// d_scalars: count x 4 words, d_points: count x 8 canonical words or nullptr for Base8, d_out: 8 words per result, out_stride_words
+// apart (0: packed, the input of poseidon::hash_batch of arity 2); device pointers
+inline void mul_batch(const Context& c, const void* d_scalars, const void* d_points, size_t count, void* d_out, size_t out_stride_words = 0) {
+    c.check(zk_babyjub_mul_batch(c.get(), d_scalars, d_points, count, d_out, out_stride_words), "babyjub::mul_batch");
+}
+}  // namespace babyjub
 
 // zk_poseidon_tree_*: a binary Merkle tree over Poseidon of arity 2 that stays on the device; paths() writes leaf | siblings and the
 // direction bits in the layout Mixgen::run reads as d_in_fields and d_in_bits

@@ -1069,6 +1069,38 @@ class Context:
         torch.cuda.synchronize(dev)
         return PoseidonTree(self, d.data_ptr(), a.shape[0], depth)
 
+    # ---- Baby Jubjub (zksnark_rs_amd.babyjub) ----
+    def babyjub_mul_batch(self, scalars, points=None, count=None, d_out_ptr=None, out_stride_words=0):
+        """zk_babyjub_mul_batch: [scalars[j]] points[j], or [scalars[j]] Base8 where points is None.  Device form (count and d_out_ptr
+        given): scalars and points are device pointers to count x 4 words and count x 8 canonical words (points may be None); the
+        affine results go to the 8 words at d_out_ptr + j * out_stride_words words (0 or 8: packed, the input of poseidon_hash_batch
+        of arity 2).  Host form: scalars = integers below 2^256 or (count, 4) uint64, points = pairs of integers or (count, 2, 4)
+        uint64 -> (count, 2, 4) uint64, staged through torch tensors on the context's device."""
+        if d_out_ptr is not None:
+            self._check(self.lib.zk_babyjub_mul_batch(self.ptr, C.c_void_p(scalars), C.c_void_p(points) if points is not None else None, count,
+                                                      C.c_void_p(d_out_ptr), out_stride_words))
+            return None
+        import torch
+        from .babyjub import scalars_to_words
+        s = scalars if isinstance(scalars, np.ndarray) else scalars_to_words(scalars)
+        s = np.ascontiguousarray(s, dtype=np.uint64).reshape(-1, 4)
+        n = s.shape[0]
+        dev = "cuda:%d" % self.device
+        pad = lambda a, width: np.ascontiguousarray(np.vstack([a.reshape(-1, width), np.zeros((1, width), np.uint64)]))   # noqa: E731 -- never an empty tensor
+        d_s = torch.from_numpy(pad(s, 4).view(np.int64)).to(dev)
+        d_p = None
+        if points is not None:
+            p = points if isinstance(points, np.ndarray) else np.stack([ints_to_limbs([int(x), int(y)]) for x, y in points]) if n else np.zeros((0, 2, 4), np.uint64)
+            p = np.ascontiguousarray(p, dtype=np.uint64).reshape(-1, 8)
+            if p.shape[0] != n:
+                raise ZkError(_lib.ZK_ERR_ARG, "babyjub: %d scalars and %d points" % (n, p.shape[0]))
+            d_p = torch.from_numpy(pad(p, 8).view(np.int64)).to(dev)
+        d_out = torch.zeros((n + 1, 8), dtype=torch.int64, device=dev)
+        torch.cuda.synchronize(dev)
+        self._check(self.lib.zk_babyjub_mul_batch(self.ptr, C.c_void_p(d_s.data_ptr()), C.c_void_p(d_p.data_ptr()) if d_p is not None else None, n,
+                                                  C.c_void_p(d_out.data_ptr()), 0))
+        return d_out.cpu().numpy().view(np.uint64)[:n].reshape(n, 2, 4)
+
     # ---- profiling ----
     def profile_reset(self):
         self._check(self.lib.zk_profile_reset(self.ptr))

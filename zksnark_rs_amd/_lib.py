@@ -206,6 +206,16 @@ SIGNATURES = {
     "zk_poseidon_tree_paths": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
     "zk_poseidon_tree_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "zk_poseidon_tree_append": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "zk_builder_babyjub_assert_on_curve": (C.c_int, [C.c_void_p, u32p]),
+    "zk_builder_babyjub_add": (C.c_int, [C.c_void_p, u32p, u32p, u32p]),
+    "zk_builder_babyjub_mul_fixed": (C.c_int, [C.c_void_p, u32p, C.c_size_t, u32p]),
+    "zk_builder_babyjub_mul": (C.c_int, [C.c_void_p, u32p, u32p, C.c_size_t, u32p]),
+    "zk_builder_babyjub_affine": (C.c_int, [C.c_void_p, u32p, u32p]),
+    "zk_babyjub_params": (C.c_int, [u64p, u64p, u64p, u64p, u64p]),
+    "zk_babyjub_on_curve": (C.c_int, [u64p]),
+    "zk_babyjub_add": (C.c_int, [u64p, u64p, u64p]),
+    "zk_babyjub_mul": (C.c_int, [u64p, u64p, u64p]),
+    "zk_babyjub_mul_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
     "zk_msm_auto_window": (C.c_int, [C.c_size_t]),
     "zk_msm_auto_window_g2": (C.c_int, [C.c_size_t]),
     "zk_circuit_qap": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),

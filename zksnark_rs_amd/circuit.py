@@ -337,6 +337,48 @@ class Builder:
         self._check(self.lib.zk_builder_merkle_root(self.ptr, leaf, sp, dp, s.size, C.byref(out)))
         return out.value
 
+    # Baby Jubjub (zksnark_rs_amd.babyjub): a point is a list of three wires [X, Y, Z], projective; an affine point is [x, y, ONE]
+    def _point(self, p, n):
+        a, ap = self._wires(p)
+        if a.size != n:
+            raise BuildErr(_lib.ZK_ERR_ARG, "builder: expected %d wires, got %d" % (n, a.size))
+        return a, ap
+
+    def babyjub_assert_on_curve(self, xy):
+        """a x^2 + y^2 = 1 + d x^2 y^2 on the wires (x, y): 4 gates, the last one an assertion without output"""
+        _, ap = self._point(xy, 2)
+        self._check(self.lib.zk_builder_babyjub_assert_on_curve(self.ptr, ap))
+
+    def babyjub_add(self, p, q):
+        """-> [X, Y, Z] of p + q: 11 gates, 10 when q[2] is ONE; right for all pairs of curve points; the operands are not asserted"""
+        _, pp = self._point(p, 3)
+        _, qp = self._point(q, 3)
+        out = np.zeros(3, np.uint32)
+        self._check(self.lib.zk_builder_babyjub_add(self.ptr, pp, qp, out.ctypes.data_as(_lib.u32p)))
+        return [int(x) for x in out]
+
+    def babyjub_mul_fixed(self, bits):
+        """-> [X, Y, Z] of [sum 2^i bits[i]] Base8 for 1..256 bit wires, each asserted to be a bit: 1414 gates for 251 bits"""
+        a, ap = self._wires(bits)
+        out = np.zeros(3, np.uint32)
+        self._check(self.lib.zk_builder_babyjub_mul_fixed(self.ptr, ap, a.size, out.ctypes.data_as(_lib.u32p)))
+        return [int(x) for x in out]
+
+    def babyjub_mul(self, p_xy, bits):
+        """-> [X, Y, Z] of [sum 2^i bits[i]] P for the affine wires p_xy, asserted on the curve, for 1..256 bit wires, each asserted
+        to be a bit: 4 + n_bits + 2 + 19 (n_bits - 1) gates"""
+        _, pp = self._point(p_xy, 2)
+        a, ap = self._wires(bits)
+        out = np.zeros(3, np.uint32)
+        self._check(self.lib.zk_builder_babyjub_mul(self.ptr, pp, ap, a.size, out.ctypes.data_as(_lib.u32p)))
+        return [int(x) for x in out]
+
+    def babyjub_affine(self, p, xy):
+        """pins the existing wires xy as the affine form of the point p: x Z = X and y Z = Y, 4 gates"""
+        _, pp = self._point(p, 3)
+        _, ap = self._point(xy, 2)
+        self._check(self.lib.zk_builder_babyjub_affine(self.ptr, pp, ap))
+
     def pack_bytes(self, wires, bytes_per_element=16):
         """Word8s (or their wires, flat) -> a list of packed wires, bytes_per_element (at most 31) bytes each, little-endian per
         element: a 32-byte digest is [int.from_bytes(d[:16], "little"), int.from_bytes(d[16:], "little")]"""

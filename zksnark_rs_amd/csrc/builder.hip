@@ -1,5 +1,5 @@
-// builder.hip -- zk_builder_*: the C ABI over builder.hpp, and zk_poseidon_hash / zk_poseidon_params over poseidon.hpp (host code only;
-// no context, no device).
+// builder.hip -- zk_builder_*: the C ABI over builder.hpp, zk_poseidon_hash / zk_poseidon_params over poseidon.hpp and zk_babyjub_params /
+// _on_curve / _add / _mul over babyjub.hpp (host code only; no context, no device).
 #include "builder.hpp"
 
 namespace zk {
@@ -122,6 +122,37 @@ int zk_builder_merkle_root(zk_builder* b, uint32_t leaf, const uint32_t* sibling
         *out = o.merkle_root(leaf, siblings, dirs, depth);
     });
 }
+int zk_builder_babyjub_assert_on_curve(zk_builder* b, const uint32_t xy[2]) {
+    return builder_guard(b, [&](BuilderOps& o) {
+        if (!xy) BuilderOps::fail("null array");
+        o.known(xy[0]); o.known(xy[1]);
+        o.babyjub_assert_on_curve(xy[0], xy[1]);
+    });
+}
+int zk_builder_babyjub_add(zk_builder* b, const uint32_t p[3], const uint32_t q[3], uint32_t out[3]) {
+    return builder_guard(b, [&](BuilderOps& o) {
+        if (!p || !q || !out) BuilderOps::fail("null array");
+        o.babyjub_add(p, q, out);
+    });
+}
+int zk_builder_babyjub_mul_fixed(zk_builder* b, const uint32_t* bits, size_t n_bits, uint32_t out[3]) {
+    return builder_guard(b, [&](BuilderOps& o) {
+        if (!out || (n_bits && !bits)) BuilderOps::fail("null array");
+        o.babyjub_mul_fixed(bits, n_bits, out);
+    });
+}
+int zk_builder_babyjub_mul(zk_builder* b, const uint32_t p_xy[2], const uint32_t* bits, size_t n_bits, uint32_t out[3]) {
+    return builder_guard(b, [&](BuilderOps& o) {
+        if (!p_xy || !out || (n_bits && !bits)) BuilderOps::fail("null array");
+        o.babyjub_mul(p_xy, bits, n_bits, out);
+    });
+}
+int zk_builder_babyjub_affine(zk_builder* b, const uint32_t p[3], const uint32_t xy[2]) {
+    return builder_guard(b, [&](BuilderOps& o) {
+        if (!p || !xy) BuilderOps::fail("null array");
+        o.babyjub_affine(p, xy);
+    });
+}
 int zk_builder_finish(zk_builder* b, const uint32_t* verify_wires, size_t n_verify, zk_circuit** out) {
     if (!out) return ZK_ERR_ARG;
     *out = nullptr;
@@ -137,5 +168,12 @@ int zk_poseidon_hash(const uint64_t* inputs, size_t arity, uint64_t out[4]) {
 int zk_poseidon_params(size_t arity, unsigned* rf, unsigned* rp, uint64_t* round_constants, uint64_t* mds) {
     try { return poseidon_params_words(arity, rf, rp, round_constants, mds); } catch (...) { return ZK_ERR_ARG; }
 }
+
+int zk_babyjub_params(uint64_t a[4], uint64_t d[4], uint64_t order[4], uint64_t base8[8], uint64_t generator[8]) {
+    return babyjub_params_words(a, d, order, base8, generator);
+}
+int zk_babyjub_on_curve(const uint64_t p[8]) { return babyjub_on_curve_words(p); }
+int zk_babyjub_add(const uint64_t p[8], const uint64_t q[8], uint64_t out[8]) { return babyjub_add_words(p, q, out); }
+int zk_babyjub_mul(const uint64_t scalar[4], const uint64_t* p, uint64_t out[8]) { return babyjub_mul_words(scalar, p, out); }
 
 }  // extern "C"

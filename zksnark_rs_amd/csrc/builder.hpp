@@ -13,12 +13,13 @@
 // What differs, on purpose: wires are numbered and ordered deterministically (the reference iterates a HashMap); entries on the
 // constant-zero wire are dropped instead of becoming a witness wire that no constraint pins; its builder -> DummyRep conversion
 // (num_wires empty rows in front) is not reproduced; zk_builder_assert_bit and zk_builder_pack exist, and so do the Poseidon
-// gadgets (zk_builder_poseidon, zk_builder_merkle_root: general sub-circuits over linear forms, see BuilderOps::Form).  Header-only and
-// free of device code, so tests/cpp/builder_host.hip compiles it alone under the sanitizers.
+// gadgets (zk_builder_poseidon, zk_builder_merkle_root: general sub-circuits over linear forms, see BuilderOps::Form) and the Baby Jubjub
+// gadgets over the same forms (zk_builder_babyjub_*).  Header-only and free of device code, so tests/cpp/builder_host.hip compiles it alone under the sanitizers.
 #pragma once
 #include <array>
 #include <map>
 #include "circuit.hpp"
+#include "babyjub.hpp"
 #include "poseidon.hpp"
 
 struct zk_builder {
@@ -184,6 +185,166 @@ struct BuilderOps {
             cur = poseidon_forms(pair, 2);
         }
         return cur;
+    }
+
+    // ---- Baby Jubjub (babyjub.hpp) as general sub-circuits over linear forms ----
+    // A point is three wires (X : Y : Z); an affine point is (x, y, wire 1).  Nothing here divides: the gadgets evaluate the projective
+    // formulas forward, and zk_builder_babyjub_affine pins affine coordinates the caller supplies.
+    static Form form_const(const Fr& c) {
+        Form f;
+        if (!c.is_zero()) f[1] = c;
+        return f;
+    }
+    static Form form_sum(const Form& a, const Form& x, const Fr& scale) {
+        Form f = a;
+        form_add(f, x, scale);
+        return f;
+    }
+    // (l) * (r) = 0: a sub-circuit without output, as assert_bit
+    void assert_forms(const Form& l, const Form& r) {
+        const uint32_t l0 = (uint32_t)b.terms.size();
+        push_form(l);
+        const uint32_t r0 = (uint32_t)b.terms.size();
+        push_form(r);
+        b.boolean = false;
+        close_sub(l0, r0, false, BOOL_NONE, 0, 0);
+    }
+    // x x = u, y y = v, u v = w, (a u + v - 1 - d w) * 1 = 0
+    void babyjub_assert_on_curve(uint32_t x, uint32_t y) {
+        const BjConsts k = babyjub_consts();
+        const Fr one = Fr::one();
+        const Form u = form_of(sub_forms(form_of(x), form_of(x))), v = form_of(sub_forms(form_of(y), form_of(y)));
+        const Form w = form_of(sub_forms(u, v));
+        Form eq;
+        form_add(eq, u, k.a);
+        form_add(eq, v, one);
+        form_add(eq, form_const(one), -one);
+        form_add(eq, w, -k.d);
+        assert_forms(eq, form_of(1));
+    }
+    // add-2008-bbjlp; z2 == nullptr: the second operand is affine and A = Z1 costs no gate (10 gates instead of 11)
+    void babyjub_add_forms(const Form& x1, const Form& y1, const Form& z1, const Form& x2, const Form& y2, const Form* z2, uint32_t out[3]) {
+        const BjConsts k = babyjub_consts();
+        const Fr one = Fr::one(), minus = -Fr::one();
+        const Form A = z2 ? form_of(sub_forms(z1, *z2)) : z1;
+        const Form B = form_of(sub_forms(A, A));
+        const Form C = form_of(sub_forms(x1, x2)), D = form_of(sub_forms(y1, y2));
+        const Form E = form_of(sub_forms(C, D));
+        const Form H = form_of(sub_forms(form_sum(x1, y1, one), form_sum(x2, y2, one)));
+        const Form F = form_sum(B, E, -k.d), G = form_sum(B, E, k.d);
+        const Form AF = form_of(sub_forms(A, F)), AG = form_of(sub_forms(A, G));
+        out[0] = sub_forms(AF, form_sum(form_sum(H, C, minus), D, minus));
+        out[1] = sub_forms(AG, form_sum(D, C, -k.a));
+        out[2] = sub_forms(F, G);
+    }
+    // dbl-2008-bbjlp: 7 gates
+    void babyjub_dbl_forms(const Form& x, const Form& y, const Form& z, uint32_t out[3]) {
+        const BjConsts k = babyjub_consts();
+        const Fr one = Fr::one(), minus = -Fr::one();
+        const Form s = form_sum(x, y, one);
+        const Form B = form_of(sub_forms(s, s)), C = form_of(sub_forms(x, x)), D = form_of(sub_forms(y, y)), H = form_of(sub_forms(z, z));
+        const Form E = form_sum(Form(), C, k.a);
+        const Form F = form_sum(E, D, one), J = form_sum(F, H, -(one + one));
+        out[0] = sub_forms(form_sum(form_sum(B, C, minus), D, minus), J);
+        out[1] = sub_forms(F, form_sum(E, D, minus));
+        out[2] = sub_forms(F, J);
+    }
+    void babyjub_add(const uint32_t p[3], const uint32_t q[3], uint32_t out[3]) {
+        for (int i = 0; i < 3; ++i) { known(p[i]); known(q[i]); }
+        const Form z2 = form_of(q[2]);
+        uint32_t o[3];                                      // out may alias p or q
+        babyjub_add_forms(form_of(p[0]), form_of(p[1]), form_of(p[2]), form_of(q[0]), form_of(q[1]), q[2] == 1 ? nullptr : &z2, o);
+        std::copy(o, o + 3, out);
+    }
+    // x Z = t, (t - X) * 1 = 0, and the same for y
+    void babyjub_affine(const uint32_t p[3], const uint32_t xy[2]) {
+        for (int i = 0; i < 3; ++i) known(p[i]);
+        known(xy[0]); known(xy[1]);
+        for (int i = 0; i < 2; ++i) {
+            const Form t = form_of(sub_forms(form_of(xy[i]), form_of(p[2])));
+            assert_forms(form_sum(t, form_of(p[i]), -Fr::one()), form_of(1));
+        }
+    }
+    // The point table[sum 2^i bits[i]] of a table of 2^n affine points, n <= 3, as two forms: multilinear in the bits, the coefficient of
+    // a product of bits is the alternating sum of the entries below it; the products b0 b1, b0 b2, b1 b2, (b0 b1) b2 are the gates.
+    void babyjub_select(const uint32_t* bits, size_t n, const BjAffine* table, Form& x, Form& y) {
+        Form prod[8];
+        prod[0] = form_of(1);
+        for (size_t i = 0; i < n; ++i) prod[(size_t)1 << i] = form_of(bits[i]);
+        if (n >= 2) prod[3] = form_of(sub_forms(form_of(bits[0]), form_of(bits[1])));
+        if (n == 3) {
+            prod[5] = form_of(sub_forms(form_of(bits[0]), form_of(bits[2])));
+            prod[6] = form_of(sub_forms(form_of(bits[1]), form_of(bits[2])));
+            prod[7] = form_of(sub_forms(prod[3], form_of(bits[2])));
+        }
+        x.clear(); y.clear();
+        for (unsigned mask = 0; mask < (1u << n); ++mask) {
+            Fr cx = Fr::zero(), cy = Fr::zero();
+            for (unsigned s = 0; s < (1u << n); ++s) {
+                if (s & ~mask) continue;
+                const bool odd = __builtin_popcount(mask ^ s) & 1;
+                cx = odd ? cx - table[s].x : cx + table[s].x;
+                cy = odd ? cy - table[s].y : cy + table[s].y;
+            }
+            form_add(x, prod[mask], cx);
+            form_add(y, prod[mask], cy);
+        }
+    }
+    static constexpr unsigned BABYJUB_GADGET_WINDOW = 3;
+    // [sum 2^i bits[i]] Base8: every bit asserted, 3-bit windows from the least significant, the window's point selected from constant
+    // multiples of Base8, one mixed addition per further window; the first window is the accumulator itself
+    void babyjub_mul_fixed(const uint32_t* bits, size_t n, uint32_t out[3]) {
+        if (n < 1 || n > 256) fail("babyjub_mul_fixed: n_bits must be in 1..256, got " + std::to_string(n));
+        for (size_t i = 0; i < n; ++i) known(bits[i]);
+        const std::vector<uint32_t> bit(bits, bits + n);   // out may alias bits
+        const unsigned W = BABYJUB_GADGET_WINDOW;
+        static const std::vector<BjAffine> table = babyjub_window_table(W, (256 + W - 1) / W);
+        for (size_t i = 0; i < n; ++i) assert_bit(bit[i]);
+        Form acc[3], x2, y2;
+        for (size_t at = 0; at < n; at += W) {
+            babyjub_select(bit.data() + at, std::min<size_t>(W, n - at), table.data() + ((at / W) << W), x2, y2);
+            if (at == 0) { acc[0] = x2; acc[1] = y2; acc[2] = form_of(1); continue; }
+            babyjub_add_forms(acc[0], acc[1], acc[2], x2, y2, nullptr, out);
+            for (int i = 0; i < 3; ++i) acc[i] = form_of(out[i]);
+        }
+        if (n <= W) {                                       // one window: the two forms become wires
+            out[0] = sub_forms(acc[0], form_of(1));
+            out[1] = sub_forms(acc[1], form_of(1));
+            out[2] = 1;
+        }
+    }
+    // [sum 2^i bits[i]] P for an affine P the caller supplies: P asserted on the curve, every bit asserted, from the most significant
+    // bit: the selection b Px, b (Py - 1) of P or the identity, and per further bit a doubling, the selection and a mixed addition
+    void babyjub_mul(const uint32_t p_xy[2], const uint32_t* bits, size_t n, uint32_t out[3]) {
+        if (n < 1 || n > 256) fail("babyjub_mul: n_bits must be in 1..256, got " + std::to_string(n));
+        known(p_xy[0]); known(p_xy[1]);
+        for (size_t i = 0; i < n; ++i) known(bits[i]);
+        const std::vector<uint32_t> bit(bits, bits + n);
+        const uint32_t px = p_xy[0], py = p_xy[1];
+        babyjub_assert_on_curve(px, py);
+        for (size_t i = 0; i < n; ++i) assert_bit(bit[i]);
+        const Fr one = Fr::one();
+        const Form fx = form_of(px), fy1 = form_sum(form_of(py), form_const(one), -one);
+        Form x2, y2;
+        auto select = [&](uint32_t bw) {
+            x2 = form_of(sub_forms(form_of(bw), fx));
+            y2 = form_sum(form_of(sub_forms(form_of(bw), fy1)), form_const(one), one);
+        };
+        select(bit[n - 1]);
+        if (n == 1) {
+            out[0] = x2.begin()->first;
+            out[1] = sub_forms(y2, form_of(1));
+            out[2] = 1;
+            return;
+        }
+        Form acc[3] = {x2, y2, form_of(1)};
+        for (size_t i = n - 1; i-- > 0;) {
+            uint32_t d[3];
+            babyjub_dbl_forms(acc[0], acc[1], acc[2], d);
+            select(bit[i]);
+            babyjub_add_forms(form_of(d[0]), form_of(d[1]), form_of(d[2]), x2, y2, nullptr, out);
+            for (int k = 0; k < 3; ++k) acc[k] = form_of(out[k]);
+        }
     }
 
     // ---- mod.rs:723-798, 939-950 ----
