@@ -11,6 +11,7 @@ from zksnark_rs_amd import babyjub
 from zksnark_rs_amd.circuit import Builder, BuildErr, ParseErr
 
 import babyjub_model as bm
+from gadget_cases import Pair, check_rows, check_witness, outputs, value
 
 R = bm.R
 EDGE = bm.edge_points()
@@ -90,73 +91,6 @@ def test_refusals():
 
 
 # ---- the gadgets -----------------------------------------------------------------------------------
-class Pair:
-    """one circuit built twice: through the library and through the model"""
-
-    def __init__(self):
-        self.lib, self.model = Builder(), bm.Gadget()
-
-    def field(self):
-        a, b = self.lib.new_wire(), self.model.new_field()
-        assert a == b
-        return a
-
-    def bits(self, n):
-        a, b = self.lib.new_bits(n), self.model.new_bits(n)
-        assert a == b
-        return a
-
-    def both(self, name, *args):
-        a, b = getattr(self.lib, name)(*args), getattr(self.model, name)(*args)
-        assert a == b, name
-        return a
-
-    def finish(self, verify):
-        assert self.lib.dims() == (len(self.model.kind), len(self.model.subs))
-        c, f = self.lib.finish(verify), self.model.finish(verify)
-        f.kinds = list(self.model.kind)
-        return c, f
-
-
-def split_inputs(f, row):
-    kinds = [k for k in f.kinds if k in ("bit", "field")]
-    bits = [x for x, k in zip(row, kinds) if k == "bit"]
-    packed = bytes(sum(b << i for i, b in enumerate(bits[8 * k:8 * k + 8])) for k in range((len(bits) + 7) // 8))
-    return packed, [x for x, k in zip(row, kinds) if k == "field"]
-
-
-def check_rows(c, f):
-    assert (c.m, c.n, c.input, c.n_in) == (f.m, f.n, f.input, f.n_in)
-    for which in range(3):
-        ptr, gate, val = c.rows(which)
-        mptr, mgate, mval = f.csr(which)
-        assert [int(x) for x in ptr] == mptr and [int(x) for x in gate] == mgate and limbs_to_ints(val) == mval, which
-    assert not c.boolean
-
-
-def check_witness(c, f, row):
-    """the three host evaluators agree with the model's witness and every gate holds"""
-    want = f.evaluate(row)
-    assert f.failing_gates(want) == []
-    w = c.weights(row)
-    assert limbs_to_ints(w) == want
-    assert np.array_equal(c.weights_tape(row), w)
-    packed, fields = split_inputs(f, row)
-    assert np.array_equal(c.weights_mixed(packed, fields), w)
-    return want
-
-
-def value(f, w, point):
-    """the affine point behind three wires of a witness"""
-    v = [1 if x == 1 else w[f.wit[x]] for x in point]
-    assert v[2] != 0
-    return bm.to_affine(tuple(v))
-
-
-def outputs(point):
-    return [x for x in point if x > 1]
-
-
 def test_assert_on_curve_and_affine():
     p = Pair()
     x, y = p.field(), p.field()

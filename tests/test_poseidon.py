@@ -11,6 +11,7 @@ from zksnark_rs_amd import poseidon
 from zksnark_rs_amd.circuit import Builder, BuildErr
 
 import poseidon_model as pm
+from gadget_cases import Pair
 
 R = pm.R
 
@@ -100,32 +101,6 @@ def test_refusals():
 
 
 # ---- the gadgets -----------------------------------------------------------------------------------
-class Pair:
-    """one circuit built twice: through the library and through the model"""
-
-    def __init__(self):
-        self.lib, self.model = Builder(), pm.Gadget()
-
-    def field(self):
-        a, b = self.lib.new_wire(), self.model.new_field()
-        assert a == b
-        return a
-
-    def bits(self, n):
-        a, b = self.lib.new_bits(n), self.model.new_bits(n)
-        assert a == b
-        return a
-
-    def both(self, name, *args):
-        a, b = getattr(self.lib, name)(*args), getattr(self.model, name)(*args)
-        assert a == b, name
-        return a
-
-    def finish(self, verify):
-        assert self.lib.dims() == (len(self.model.kind), len(self.model.subs))
-        return self.lib.finish(verify), self.model.finish(verify)
-
-
 def check_against_model(c, f, input_rows):
     """rows word for word; per input row the three host evaluators agree with the model's witness and every gate holds"""
     assert (c.m, c.n, c.input, c.n_in) == (f.m, f.n, f.input, f.n_in)
