@@ -221,6 +221,14 @@ extern "C" {
     fn zk_babyjub_mul(scalar: *const u64, p: *const u64, out: *mut u64) -> c_int;
     fn zk_babyjub_mul_batch(ctx: *mut ZkCtx, d_scalars: *const c_void, d_points: *const c_void, count: usize, d_out: *mut c_void,
                             out_stride_words: usize) -> c_int;
+    // EdDSA-Poseidon on Baby Jubjub: the gadget, host sign / verify, GPU batch verification
+    fn zk_builder_eddsa_verify(b: *mut ZkBuilder, a_xy: *const u32, r8_xy: *const u32, msg: u32, s_bits: *const u32, hm_bits: *const u32) -> c_int;
+    fn zk_eddsa_challenge(r8: *const u64, a: *const u64, msg: *const u64, out: *mut u64) -> c_int;
+    fn zk_eddsa_public_key(k: *const u64, out: *mut u64) -> c_int;
+    fn zk_eddsa_sign(k: *const u64, nonce_key: *const u64, msg: *const u64, r8_out: *mut u64, s_out: *mut u64) -> c_int;
+    fn zk_eddsa_verify(a: *const u64, msg: *const u64, r8: *const u64, s: *const u64, status: *mut c_int) -> c_int;
+    fn zk_eddsa_verify_batch(ctx: *mut ZkCtx, d_points_msg: *const c_void, d_s: *const c_void, count: usize, d_status: *mut c_void,
+                             d_bits_out: *mut c_void, bits_stride_bytes: usize) -> c_int;
     // Poseidon over Fr (circomlib's parameter sets): host hash, GPU batch hashing, a device-resident Merkle tree and its paths
     fn zk_poseidon_hash(inputs: *const u64, arity: usize, out: *mut u64) -> c_int;
     fn zk_poseidon_params(arity: usize, rf: *mut c_uint, rp: *mut c_uint, round_constants: *mut u64, mds: *mut u64) -> c_int;
@@ -1350,6 +1358,11 @@ impl GpuCircuitBuilder {
     }
     /// pins the existing wires xy as the affine form of p: 4 gates
     pub fn babyjub_affine(&mut self, p: [WireId; 3], xy: [WireId; 2]) { self.ok(unsafe { zk_builder_babyjub_affine(self.0, p.as_ptr(), xy.as_ptr()) }) }
+    /// EdDSA-Poseidon: [S] Base8 = R8 + [8] ([hm] A), hm = H6(R8, A, M), over the affine wires of A and R8, the message wire, the 251 bit
+    /// wires of S and the 254 bit wires of hm, which the caller supplies (eddsa_verify_batch writes them): 73384 gates
+    pub fn eddsa_verify(&mut self, a_xy: [WireId; 2], r8_xy: [WireId; 2], msg: WireId, s_bits: &[WireId; 251], hm_bits: &[WireId; 254]) {
+        self.ok(unsafe { zk_builder_eddsa_verify(self.0, a_xy.as_ptr(), r8_xy.as_ptr(), msg, s_bits.as_ptr(), hm_bits.as_ptr()) })
+    }
     pub fn fan_in(&mut self, inputs: &[WireId], g: Gate) -> WireId {
         let mut out = 0u32;
         self.ok(unsafe { zk_builder_fan_in(self.0, g as c_int, inputs.as_ptr(), inputs.len(), &mut out) });
@@ -1523,6 +1536,38 @@ pub fn babyjub_params() -> ([u64; 4], [u64; 4], [u64; 4], [u64; 8], [u64; 8]) {
 /// zk_babyjub_mul_batch: `count` scalar multiplications, device to device; d_points null: Base8; out_stride_words 0: packed
 pub fn babyjub_mul_batch(ctx: *mut ZkCtx, d_scalars: *const c_void, d_points: *const c_void, count: usize, d_out: *mut c_void, out_stride_words: usize) {
     unsafe { check(ctx, zk_babyjub_mul_batch(ctx, d_scalars, d_points, count, d_out, out_stride_words)) }
+}
+
+/// EdDSA-Poseidon on Baby Jubjub (include/zkgpu.h states the scheme).  The status of one signature, the lowest that applies
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum EddsaStatus { Valid = 0, Range = 1, KeyOffCurve = 2, ROffCurve = 3, SRange = 4, Mismatch = 5 }
+/// H6(R8.x, R8.y, A.x, A.y, M) for any five field elements, no curve check.  None: an element >= r
+pub fn eddsa_challenge(r8: &[u64; 8], a: &[u64; 8], msg: &[u64; 4]) -> Option<[u64; 4]> {
+    let mut out = [0u64; 4];
+    if unsafe { zk_eddsa_challenge(r8.as_ptr(), a.as_ptr(), msg.as_ptr(), out.as_mut_ptr()) } == 0 { Some(out) } else { None }
+}
+/// [k] Base8.  None: k == 0 or k >= l
+pub fn eddsa_public_key(k: &[u64; 4]) -> Option<[u64; 8]> {
+    let mut out = [0u64; 8];
+    if unsafe { zk_eddsa_public_key(k.as_ptr(), out.as_mut_ptr()) } == 0 { Some(out) } else { None }
+}
+/// (R8, S), deterministic.  None: k == 0, k >= l, nonce_key >= r or msg >= r
+pub fn eddsa_sign(k: &[u64; 4], nonce_key: &[u64; 4], msg: &[u64; 4]) -> Option<([u64; 8], [u64; 4])> {
+    let (mut r8, mut s) = ([0u64; 8], [0u64; 4]);
+    if unsafe { zk_eddsa_sign(k.as_ptr(), nonce_key.as_ptr(), msg.as_ptr(), r8.as_mut_ptr(), s.as_mut_ptr()) } == 0 { Some((r8, s)) } else { None }
+}
+/// a malformed signature is a verdict, not an error
+pub fn eddsa_verify(a: &[u64; 8], msg: &[u64; 4], r8: &[u64; 8], s: &[u64; 4]) -> EddsaStatus {
+    let mut status: c_int = 5;
+    unsafe { zk_eddsa_verify(a.as_ptr(), msg.as_ptr(), r8.as_ptr(), s.as_ptr(), &mut status) };
+    match status { 0 => EddsaStatus::Valid, 1 => EddsaStatus::Range, 2 => EddsaStatus::KeyOffCurve, 3 => EddsaStatus::ROffCurve, 4 => EddsaStatus::SRange,
+                   _ => EddsaStatus::Mismatch }
+}
+/// zk_eddsa_verify_batch: `count` verdicts, device to device; d_points_msg: count x 20 words (A.x, A.y, R8.x, R8.y, M), d_s: count x 4,
+/// d_status: count x u32; d_bits_out null, or rows of bits_stride_bytes (>= 64, a multiple of 8) with the bits of S and of hm
+pub fn eddsa_verify_batch(ctx: *mut ZkCtx, d_points_msg: *const c_void, d_s: *const c_void, count: usize, d_status: *mut c_void,
+                          d_bits_out: *mut c_void, bits_stride_bytes: usize) {
+    unsafe { check(ctx, zk_eddsa_verify_batch(ctx, d_points_msg, d_s, count, d_status, d_bits_out, bits_stride_bytes)) }
 }
 
 /// zk_poseidon_tree_*: a binary Merkle tree over Poseidon of arity 2 that stays on the device; paths() writes leaf | siblings and the

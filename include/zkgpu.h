@@ -437,6 +437,28 @@ int zk_builder_babyjub_mul_fixed(zk_builder* b, const uint32_t* bits, size_t n_b
 int zk_builder_babyjub_mul(zk_builder* b, const uint32_t p_xy[2], const uint32_t* bits, size_t n_bits, uint32_t out[3]);
 /* Pins the existing wires xy as the affine form of p: x Z = t, (t - X) * 1 = 0, and the same for y: 4 gates, no new point. */
 int zk_builder_babyjub_affine(zk_builder* b, const uint32_t p[3], const uint32_t xy[2]);
+/* The statement "the owner of A signed M" (see "EdDSA-Poseidon" below): [S] Base8 = R8 + [8] ([hm] A) with hm = H6(R8.x, R8.y, A.x, A.y, M),
+ * over the affine wires a_xy and r8_xy, the message wire, and the 251 bits of S and the 254 bits of hm, least significant first.  The
+ * hm bits are inputs the caller supplies, because the tape cannot decompose an element; zk_eddsa_verify_batch produces them on the
+ * device.  Emitted from the existing gadgets, in this order:
+ *   zk_builder_babyjub_assert_on_curve(R8)                                                                       4 gates
+ *   zk_builder_compare(ZK_CMP_LESS, s_bits, the bits of l as ZK_WIRE_ONE / ZK_WIRE_ZERO, 251), then (lt - 1) * 1 = 0    32881
+ *   the same for hm_bits against the bits of r over 254 bits: circomlib's alias check -- without it a prover may use
+ *   hm + r wherever that is below 2^254                                                                          33655
+ *   H6 over the five forms: 3 (8 * 6 + 60) + 1                                                                   325
+ *   (sum_i 2^i hm_bits[i] - digest) * 1 = 0, one assertion over 254 bits (zk_builder_pack stops at 253)            1
+ *   zk_builder_babyjub_mul(A, hm_bits, 254), which asserts A on the curve and every hm bit                        5067
+ *   three doublings (7 each) and the mixed addition of R8 (10)                                                    31
+ *   zk_builder_babyjub_mul_fixed(s_bits, 251), which asserts every S bit                                          1414
+ *   per coordinate X1 Z2 = t1, X2 Z1 = t2, (t1 - t2) * 1 = 0: an assertion has no output, so a product costs a gate
+ *   on either side                                                                                                6
+ * 73384 gates.  The two comparators are nine tenths of that: the reference's greater_than folds its equalities anew for every bit
+ * (n^2 / 2 AND gates).  They are boolean-class gates, so zk_mixgen_* runs them in the bit-sliced core; the rest is the field tail.
+ * No affine wire and no division.  Not offered: circomlib's `enabled` input, and its rejection of keys with 8 A = identity (that
+ * needs an inverse hint the tape cannot compute; zk_eddsa_verify has no such check either).  ZK_ERR_ARG with text: an unknown wire, a
+ * null array; a refused call emits nothing. */
+int zk_builder_eddsa_verify(zk_builder* b, const uint32_t a_xy[2], const uint32_t r8_xy[2], uint32_t msg, const uint32_t s_bits[251],
+                            const uint32_t hm_bits[254]);
 /* The circuit as an ordinary zk_circuit (free it with zk_circuit_free; the builder may be freed before or after).  Witness order: the
  * constant 1, the verify wires in the order given (qap.input = n_verify), the remaining input wires in creation order, the remaining
  * wires by id.  Sub-circuit k is gate k (0-based), at root k + 1 of zk_circuit_qap / _qap_sparse.  ZK_ERR_ARG with text: a verify wire
@@ -629,6 +651,55 @@ int zk_babyjub_mul(const uint64_t scalar[4], const uint64_t* p, uint64_t out[8])
 #define ZK_BABYJUB_FIXED_WINDOW 4
 #define ZK_BABYJUB_VAR_WINDOW 2
 int zk_babyjub_mul_batch(zk_ctx* ctx, const void* d_scalars, const void* d_points, size_t count, void* d_out, size_t out_stride_words);
+
+/* ------------------------------------------------------------------------------------------
+ * EdDSA-Poseidon on Baby Jubjub (csrc/eddsa.hpp, csrc/eddsa.hip).  The scheme, the same in every layer:
+ *   curve, generator     those above; l is the order of Base8
+ *   secret key           a scalar k, 0 < k < l;  public key A = [k] Base8;  nonce key: a field element n < r
+ *   H6(a, b, c, d, e)    Poseidon of width 6 over the state [0, a, b, c, d, e]: R_F = 8, R_P = 60, x^5, element 0 is the digest; the
+ *                        round structure and the Grain procedure of the three public widths.  H6(1, 2, 3, 4, 5) =
+ *                        0x0dab9449e4a1398a15224c0b15a49d598b2174d305a316c918125f8feeb123c0, the value circomlibjs and
+ *                        go-iden3-crypto publish.  Width 6 is reachable through the zk_eddsa_* calls only: zk_poseidon_* refuse arity 5.
+ *   Sign(k, n, M), M < r rho = H6(n, M, 0, 0, 0) mod l;  R8 = [rho] Base8;  hm = H6(R8.x, R8.y, A.x, A.y, M);  S = (rho + 8 hm k) mod l.
+ *                        The signature is (R8, S), 12 words.  Signing is deterministic.
+ *   Verify(A, M, R8, S)  valid when all six words of A, R8, M, S are canonical (< r), A and R8 are on the curve, S < l, and
+ *                        [S] Base8 = R8 + [8] ([hm] A) with hm taken as the full integer below r, NOT reduced mod l.  8 hm can reach
+ *                        2^257: [hm] A is computed and doubled three times; 8 hm is never a scalar.
+ * This is the equation of circomlibjs' verifyPoseidon: a signature made by circomlib verifies here, its key given as k = pruned >> 3.
+ * Not offered: circomlib's key derivation from 32 bytes by Blake-512 (its rho comes from Blake-512, ours from H6; a verifier cannot
+ * tell), and a rejection of keys of small order: with A = (0, 1) every S with R8 = [S] Base8 is valid, as in verifyPoseidon.
+ * One status per signature, the lowest applicable: */
+#define ZK_EDDSA_VALID 0
+#define ZK_EDDSA_RANGE 1           /* a word pattern of A, R8, M or S is >= r */
+#define ZK_EDDSA_KEY_OFF_CURVE 2
+#define ZK_EDDSA_R_OFF_CURVE 3
+#define ZK_EDDSA_S_RANGE 4         /* S >= l */
+#define ZK_EDDSA_MISMATCH 5
+/* out = H6(r8.x, r8.y, a.x, a.y, msg) on the host, no context.  A range check only and deliberately NO curve check: any five elements
+ * hash.  ZK_ERR_ARG: a null pointer.  ZK_ERR_RANGE: a word pattern >= r. */
+int zk_eddsa_challenge(const uint64_t r8[8], const uint64_t a[8], const uint64_t msg[4], uint64_t out[4]);
+/* out = [k] Base8.  ZK_ERR_ARG: a null pointer.  ZK_ERR_RANGE: k == 0 or k >= l. */
+int zk_eddsa_public_key(const uint64_t k[4], uint64_t out[8]);
+/* (r8_out, s_out) = Sign(k, nonce_key, msg) on the host, no context; k, rho and the nonce key are wiped from the call's locals before
+ * it returns.  ZK_ERR_ARG: a null pointer.  ZK_ERR_RANGE: k == 0, k >= l, nonce_key >= r or msg >= r; nothing is written then. */
+int zk_eddsa_sign(const uint64_t k[4], const uint64_t nonce_key[4], const uint64_t msg[4], uint64_t r8_out[8], uint64_t s_out[4]);
+/* *status = ZK_EDDSA_* for one signature on the host, no context.  Returns ZK_OK for every signature: a malformed one is a verdict, not
+ * an error.  ZK_ERR_ARG: a null pointer. */
+int zk_eddsa_verify(const uint64_t a[8], const uint64_t msg[4], const uint64_t r8[8], const uint64_t s[4], int* status);
+/* `count` verdicts on the GPU, one signature per lane.  d_points_msg: count x 20 words, (A.x, A.y, R8.x, R8.y, M) per signature --
+ * the five ZK_WIRE_FIELD inputs of zk_builder_eddsa_verify's circuit in zk_mixgen_run's d_in_fields layout; d_s: count x 4 words;
+ * d_status: count x uint32, ZK_EDDSA_*.  d_bits_out may be NULL; otherwise row j, at d_bits_out + j * bits_stride_bytes, receives 64
+ * bytes: the 251 low bits of S, then the 254 bits of hm, least significant first, then 7 zero bits -- zk_mixgen_run's d_in_bits for a
+ * circuit whose bit inputs were made in that order -- and bytes of a row past the 64th are not written.  A row is all zero where the
+ * status is ZK_EDDSA_RANGE.  The chain zk_eddsa_verify_batch -> zk_mixgen_run -> zk_prove_batch_submit runs device to device.
+ * Two launches: the range, curve and S < l checks with H6 (32 bytes a signature in a context buffer), then [hm] A by windows of 2
+ * bits in registers, three doublings, + R8, [S] Base8 over the table of zk_babyjub_mul_batch, and the comparison by cross
+ * multiplication: no inversion, no LDS.  Every lane runs the same instruction stream whatever its data; a defective signature
+ * changes its own status only.  All device pointers, 8-byte aligned (d_status: 4-byte).  Complete on return.  count == 0: ZK_OK,
+ * nothing touched.  ZK_ERR_ARG with text: a null or misaligned pointer; with d_bits_out, a stride below 64 or no multiple of 8.
+ * Per-signature defects are statuses and never refuse the call. */
+int zk_eddsa_verify_batch(zk_ctx* ctx, const void* d_points_msg, const void* d_s, size_t count, void* d_status, void* d_bits_out,
+                          size_t bits_stride_bytes);
 
 /* ------------------------------------------------------------------------------------------
  * CRS  (SigmaG1 / SigmaG2, groth16/mod.rs:105-121)

@@ -366,6 +366,15 @@ class Circuit {
     // pins the existing wires (x, y) as the affine form of p: 4 gates
     void babyjub_affine(const Point& p, WireId x, WireId y) { const WireId xy[2] = {x, y}; check(zk_builder_babyjub_affine(b_, p.data(), xy)); }
 
+    // EdDSA-Poseidon (eddsa::): [S] Base8 = R8 + [8] ([hm] A), hm = H6(R8, A, M), over the affine wires of A and R8, the message wire, the
+    // 251 bit wires of S and the 254 bit wires of hm (supplied by the caller; eddsa::verify_batch writes them): 73384 gates
+    template <class Wires>
+    void eddsa_verify(WireId ax, WireId ay, WireId r8x, WireId r8y, WireId msg, const Wires& s_bits, const Wires& hm_bits) {
+        if (s_bits.size() != 251 || hm_bits.size() != 254) throw Error(ZK_ERR_ARG, "eddsa_verify: 251 bit wires of S and 254 of hm are expected");
+        const WireId a[2] = {ax, ay}, r8[2] = {r8x, r8y};
+        check(zk_builder_eddsa_verify(b_, a, r8, msg, s_bits.data(), hm_bits.data()));
+    }
+
     template <class Wires>
     WireId fan_in(const Wires& inputs, Gate g) { WireId o; check(zk_builder_fan_in(b_, (int)g, inputs.data(), inputs.size(), &o)); return o; }
     template <class Wires>
@@ -553,6 +562,55 @@ inline void mul_batch(const Context& c, const void* d_scalars, const void* d_poi
     c.check(zk_babyjub_mul_batch(c.get(), d_scalars, d_points, count, d_out, out_stride_words), "babyjub::mul_batch");
 }
 }  // namespace babyjub
+
+// EdDSA-Poseidon on Baby Jubjub (zk_eddsa_*; include/zkgpu.h states the scheme): a secret key is 0 < k < l, a public key [k] Base8, a
+// signature (R8, S).  A malformed signature is a verdict (Status), not an error.
+namespace eddsa {
+enum class Status : int { Valid = ZK_EDDSA_VALID, Range = ZK_EDDSA_RANGE, KeyOffCurve = ZK_EDDSA_KEY_OFF_CURVE, ROffCurve = ZK_EDDSA_R_OFF_CURVE,
+                          SRange = ZK_EDDSA_S_RANGE, Mismatch = ZK_EDDSA_MISMATCH };
+struct Signature { babyjub::Point r8; FrLocal s; };
+namespace detail {
+inline void check(int rc, const char* range) {
+    if (rc < 0) throw Error(rc, rc == ZK_ERR_RANGE ? range : "eddsa: bad argument");
+}
+}  // namespace detail
+// H6(R8.x, R8.y, A.x, A.y, M): any five field elements, no curve check
+inline FrLocal challenge(const babyjub::Point& r8, const babyjub::Point& a, const FrLocal& msg) {
+    uint64_t r[8], p[8];
+    babyjub::detail::words(r8, r);
+    babyjub::detail::words(a, p);
+    FrLocal out;
+    detail::check(zk_eddsa_challenge(r, p, msg.w.data(), out.w.data()), "eddsa: an element is not below r");
+    return out;
+}
+inline babyjub::Point public_key(const FrLocal& k) {
+    uint64_t o[8];
+    detail::check(zk_eddsa_public_key(k.w.data(), o), "eddsa: the key is 0 or not below l");
+    return babyjub::detail::point(o);
+}
+inline Signature sign(const FrLocal& k, const FrLocal& nonce_key, const FrLocal& msg) {
+    uint64_t o[8];
+    Signature sig;
+    detail::check(zk_eddsa_sign(k.w.data(), nonce_key.w.data(), msg.w.data(), o, sig.s.w.data()),
+                  "eddsa: the key is 0 or not below l, or the nonce key or the message is not below r");
+    sig.r8 = babyjub::detail::point(o);
+    return sig;
+}
+inline Status verify(const babyjub::Point& a, const FrLocal& msg, const Signature& sig) {
+    uint64_t p[8], r[8];
+    babyjub::detail::words(a, p);
+    babyjub::detail::words(sig.r8, r);
+    int status = 0;
+    detail::check(zk_eddsa_verify(p, msg.w.data(), r, sig.s.w.data(), &status), "eddsa: bad argument");
+    return (Status)status;
+}
+// d_points_msg: count x 20 words (A.x, A.y, R8.x, R8.y, M), d_s: count x 4 words, d_status: count x uint32 (Status); d_bits_out:
+// nullptr, or rows of bits_stride_bytes with the 251 bits of S and the 254 bits of hm (Mixgen::run's d_in_bits); device pointers
+inline void verify_batch(const Context& c, const void* d_points_msg, const void* d_s, size_t count, void* d_status, void* d_bits_out = nullptr,
+                         size_t bits_stride_bytes = 64) {
+    c.check(zk_eddsa_verify_batch(c.get(), d_points_msg, d_s, count, d_status, d_bits_out, bits_stride_bytes), "eddsa::verify_batch");
+}
+}  // namespace eddsa
 
 // zk_poseidon_tree_*: a binary Merkle tree over Poseidon of arity 2 that stays on the device; paths() writes leaf | siblings and the
 // direction bits in the layout Mixgen::run reads as d_in_fields and d_in_bits

@@ -1101,6 +1101,39 @@ class Context:
                                                   C.c_void_p(d_out.data_ptr()), 0))
         return d_out.cpu().numpy().view(np.uint64)[:n].reshape(n, 2, 4)
 
+    # ---- EdDSA-Poseidon (zksnark_rs_amd.eddsa) ----
+    def eddsa_verify_batch(self, points_msg, s, count=None, d_status_ptr=None, d_bits_ptr=None, bits_stride_bytes=64, bits=False):
+        """zk_eddsa_verify_batch: one verdict (eddsa.VALID .. eddsa.MISMATCH) per signature.  Device form (count and d_status_ptr given):
+        points_msg and s are device pointers to count x 20 words (A.x, A.y, R8.x, R8.y, M) and count x 4 words; the statuses go to
+        count uint32 at d_status_ptr and, where d_bits_ptr is given, the 251 bits of S and 254 bits of hm to rows bits_stride_bytes
+        apart (zk_mixgen_run's d_in_bits).  Host form: points_msg = rows of five integers or (count, 5, 4) uint64, s = integers or
+        (count, 4) uint64 -> (count,) uint32, or (statuses, (count, bits_stride_bytes) uint8) with bits=True, staged through torch
+        tensors on the context's device."""
+        if d_status_ptr is not None:
+            self._check(self.lib.zk_eddsa_verify_batch(self.ptr, C.c_void_p(points_msg), C.c_void_p(s), count, C.c_void_p(d_status_ptr),
+                                                       C.c_void_p(d_bits_ptr) if d_bits_ptr is not None else None, bits_stride_bytes))
+            return None
+        import torch
+        from .babyjub import scalars_to_words
+        p = points_msg if isinstance(points_msg, np.ndarray) else (np.stack([ints_to_limbs([int(x) for x in row]) for row in points_msg])
+                                                                   if len(points_msg) else np.zeros((0, 5, 4), np.uint64))
+        p = np.ascontiguousarray(p, dtype=np.uint64).reshape(-1, 20)
+        sw = np.ascontiguousarray(s if isinstance(s, np.ndarray) else scalars_to_words(s), dtype=np.uint64).reshape(-1, 4)
+        n = p.shape[0]
+        if sw.shape[0] != n:
+            raise ZkError(_lib.ZK_ERR_ARG, "eddsa: %d points and %d signatures" % (n, sw.shape[0]))
+        dev = "cuda:%d" % self.device
+        pad = lambda a, width: np.ascontiguousarray(np.vstack([a.reshape(-1, width), np.zeros((1, width), np.uint64)]))   # noqa: E731 -- never an empty tensor
+        d_p = torch.from_numpy(pad(p, 20).view(np.int64)).to(dev)
+        d_s = torch.from_numpy(pad(sw, 4).view(np.int64)).to(dev)
+        d_status = torch.zeros(n + 1, dtype=torch.int32, device=dev)
+        d_bits = torch.zeros((n + 1, bits_stride_bytes), dtype=torch.uint8, device=dev) if bits else None
+        torch.cuda.synchronize(dev)
+        self._check(self.lib.zk_eddsa_verify_batch(self.ptr, C.c_void_p(d_p.data_ptr()), C.c_void_p(d_s.data_ptr()), n, C.c_void_p(d_status.data_ptr()),
+                                                   C.c_void_p(d_bits.data_ptr()) if bits else None, bits_stride_bytes))
+        status = d_status.cpu().numpy().view(np.uint32)[:n]
+        return (status, d_bits.cpu().numpy()[:n]) if bits else status
+
     # ---- profiling ----
     def profile_reset(self):
         self._check(self.lib.zk_profile_reset(self.ptr))

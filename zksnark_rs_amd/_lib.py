@@ -216,6 +216,12 @@ SIGNATURES = {
     "zk_babyjub_add": (C.c_int, [u64p, u64p, u64p]),
     "zk_babyjub_mul": (C.c_int, [u64p, u64p, u64p]),
     "zk_babyjub_mul_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
+    "zk_builder_eddsa_verify": (C.c_int, [C.c_void_p, u32p, u32p, C.c_uint32, u32p, u32p]),
+    "zk_eddsa_challenge": (C.c_int, [u64p, u64p, u64p, u64p]),
+    "zk_eddsa_public_key": (C.c_int, [u64p, u64p]),
+    "zk_eddsa_sign": (C.c_int, [u64p, u64p, u64p, u64p, u64p]),
+    "zk_eddsa_verify": (C.c_int, [u64p, u64p, u64p, u64p, C.POINTER(C.c_int)]),
+    "zk_eddsa_verify_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t]),
     "zk_msm_auto_window": (C.c_int, [C.c_size_t]),
     "zk_msm_auto_window_g2": (C.c_int, [C.c_size_t]),
     "zk_circuit_qap": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),

@@ -379,6 +379,17 @@ class Builder:
         _, ap = self._point(xy, 2)
         self._check(self.lib.zk_builder_babyjub_affine(self.ptr, pp, ap))
 
+    def eddsa_verify(self, a_xy, r8_xy, msg, s_bits, hm_bits):
+        """the statement [S] Base8 = R8 + [8] ([hm] A), hm = H6(R8, A, M) (zksnark_rs_amd.eddsa): the affine wires of A and R8, the
+        message wire, the 251 bit wires of S and the 254 bit wires of hm, which the caller supplies (Context.eddsa_verify_batch
+        writes them).  Asserts everything a verifier checks, S < l and hm < r included: 73384 gates, the two comparators 66536 of
+        them, boolean-class."""
+        _, ap = self._point(a_xy, 2)
+        _, rp = self._point(r8_xy, 2)
+        _, sp = self._point(s_bits, 251)
+        _, hp = self._point(hm_bits, 254)
+        self._check(self.lib.zk_builder_eddsa_verify(self.ptr, ap, rp, int(msg), sp, hp))
+
     def pack_bytes(self, wires, bytes_per_element=16):
         """Word8s (or their wires, flat) -> a list of packed wires, bytes_per_element (at most 31) bytes each, little-endian per
         element: a 32-byte digest is [int.from_bytes(d[:16], "little"), int.from_bytes(d[16:], "little")]"""

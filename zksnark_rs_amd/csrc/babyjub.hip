@@ -13,36 +13,12 @@
 // Every lane executes the same instruction stream whatever its scalar and point: the loops have fixed trip counts, the scalar is shifted
 // through registers with constant indices, digits select by index or by v_cndmask, and the addition law is complete, so no value is a
 // special case.  The inversion walks the public exponent r - 2 held in scalar registers.
-#include "common.hpp"
-#include "babyjub.hpp"
+#include "babyjub_dev.cuh"
 
 namespace zk {
 
-static constexpr unsigned BABYJUB_BLOCK = 256;
-static constexpr unsigned BABYJUB_FIXED_WINDOW = ZK_BABYJUB_FIXED_WINDOW, BABYJUB_FIXED_WINDOWS = 256 / BABYJUB_FIXED_WINDOW;
-static constexpr unsigned BABYJUB_VAR_WINDOW = ZK_BABYJUB_VAR_WINDOW;
-static_assert(BABYJUB_FIXED_WINDOW == 4 && BABYJUB_VAR_WINDOW == 2, "the kernels' shifts and selections are written for these windows");
 static constexpr unsigned long long BABYJUB_NO_ERROR = ~0ull;
 
-struct BabyjubState {
-    DevBuf<BjAffine> table;               // [window][digit], see above
-    DevBuf<unsigned long long> flag;      // [0] range, [1] curve
-};
-
-// 4 words of 64 bits behind an 8-byte aligned pointer -> 8 limbs
-__device__ __forceinline__ void bj_load_words(const uint64_t* __restrict__ w, uint32_t (&l)[8]) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const uint64_t v = w[i];
-        l[2 * i] = (uint32_t)v;
-        l[2 * i + 1] = (uint32_t)(v >> 32);
-    }
-}
-__device__ __forceinline__ Fr bj_load_raw(const uint64_t* __restrict__ w) {
-    Fr x;
-    bj_load_words(w, x.l);
-    return x;
-}
 __device__ __forceinline__ void bj_store(const Fr& v, uint64_t* __restrict__ w) {
     const Fr c = v.to_canonical();
 #pragma unroll
@@ -69,15 +45,6 @@ __device__ __forceinline__ void bj_store_affine(const BjPoint& p, uint64_t* __re
     const Fr zi = bj_inv(p.Z);
     bj_store(p.X * zi, out);
     bj_store(p.Y * zi, out + 4);
-}
-__device__ __forceinline__ Fr bj_pick(unsigned digit, const Fr& e0, const Fr& e1, const Fr& e2, const Fr& e3) {
-    Fr o;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const uint32_t lo = digit & 1 ? e1.l[i] : e0.l[i], hi = digit & 1 ? e3.l[i] : e2.l[i];
-        o.l[i] = digit & 2 ? hi : lo;
-    }
-    return o;
 }
 
 // grid: ceil(count / BABYJUB_BLOCK) blocks, lane j owns instance j.  out_stride: words of 64 bits between two results, >= 8.
@@ -137,13 +104,13 @@ k_babyjub_check(BjConsts k, const uint64_t* __restrict__ points, size_t count, u
     else if (!bj_on_curve(k, Fr::from_canonical(x), Fr::from_canonical(y))) atomicMin(flags + 1, (unsigned long long)j);
 }
 
-static BabyjubState& babyjub_state(zk_ctx* ctx) {
+BabyjubState& babyjub_state(zk_ctx* ctx) {
     if (!ctx->babyjub) ctx->babyjub = std::make_shared<BabyjubState>();
     BabyjubState& st = *ctx->babyjub;
     if (!st.flag.p) st.flag.alloc(2);
     return st;
 }
-static const BjAffine* babyjub_table(zk_ctx* ctx, BabyjubState& st) {
+const BjAffine* babyjub_table(zk_ctx* ctx, BabyjubState& st) {
     if (!st.table.p) {
         const std::vector<BjAffine> host = babyjub_window_table(BABYJUB_FIXED_WINDOW, BABYJUB_FIXED_WINDOWS);
         DevBuf<BjAffine> buf(host.size());

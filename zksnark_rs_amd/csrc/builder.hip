@@ -1,5 +1,6 @@
 // builder.hip -- zk_builder_*: the C ABI over builder.hpp, zk_poseidon_hash / zk_poseidon_params over poseidon.hpp and zk_babyjub_params /
-// _on_curve / _add / _mul over babyjub.hpp (host code only; no context, no device).
+// _on_curve / _add / _mul over babyjub.hpp and zk_eddsa_challenge / _public_key / _sign / _verify over eddsa.hpp (host code only; no
+// context, no device).
 #include "builder.hpp"
 
 namespace zk {
@@ -153,6 +154,13 @@ int zk_builder_babyjub_affine(zk_builder* b, const uint32_t p[3], const uint32_t
         o.babyjub_affine(p, xy);
     });
 }
+int zk_builder_eddsa_verify(zk_builder* b, const uint32_t a_xy[2], const uint32_t r8_xy[2], uint32_t msg, const uint32_t s_bits[251],
+                            const uint32_t hm_bits[254]) {
+    return builder_guard(b, [&](BuilderOps& o) {
+        if (!a_xy || !r8_xy || !s_bits || !hm_bits) BuilderOps::fail("null array");
+        o.eddsa_verify(a_xy, r8_xy, msg, s_bits, hm_bits);
+    });
+}
 int zk_builder_finish(zk_builder* b, const uint32_t* verify_wires, size_t n_verify, zk_circuit** out) {
     if (!out) return ZK_ERR_ARG;
     *out = nullptr;
@@ -175,5 +183,16 @@ int zk_babyjub_params(uint64_t a[4], uint64_t d[4], uint64_t order[4], uint64_t 
 int zk_babyjub_on_curve(const uint64_t p[8]) { return babyjub_on_curve_words(p); }
 int zk_babyjub_add(const uint64_t p[8], const uint64_t q[8], uint64_t out[8]) { return babyjub_add_words(p, q, out); }
 int zk_babyjub_mul(const uint64_t scalar[4], const uint64_t* p, uint64_t out[8]) { return babyjub_mul_words(scalar, p, out); }
+
+int zk_eddsa_challenge(const uint64_t r8[8], const uint64_t a[8], const uint64_t msg[4], uint64_t out[4]) {
+    try { return eddsa_challenge_words(r8, a, msg, out); } catch (...) { return ZK_ERR_ARG; }
+}
+int zk_eddsa_public_key(const uint64_t k[4], uint64_t out[8]) { return eddsa_public_key_words(k, out); }
+int zk_eddsa_sign(const uint64_t k[4], const uint64_t nonce_key[4], const uint64_t msg[4], uint64_t r8_out[8], uint64_t s_out[4]) {
+    try { return eddsa_sign_words(k, nonce_key, msg, r8_out, s_out); } catch (...) { return ZK_ERR_ARG; }
+}
+int zk_eddsa_verify(const uint64_t a[8], const uint64_t msg[4], const uint64_t r8[8], const uint64_t s[4], int* status) {
+    try { return eddsa_verify_words(a, msg, r8, s, status); } catch (...) { return ZK_ERR_ARG; }
+}
 
 }  // extern "C"

@@ -14,13 +14,14 @@
 // constant-zero wire are dropped instead of becoming a witness wire that no constraint pins; its builder -> DummyRep conversion
 // (num_wires empty rows in front) is not reproduced; zk_builder_assert_bit and zk_builder_pack exist, and so do the Poseidon
 // gadgets (zk_builder_poseidon, zk_builder_merkle_root: general sub-circuits over linear forms, see BuilderOps::Form) and the Baby Jubjub
-// gadgets over the same forms (zk_builder_babyjub_*).  Header-only and free of device code, so tests/cpp/builder_host.hip compiles it alone under the sanitizers.
+// gadgets over the same forms (zk_builder_babyjub_*), and zk_builder_eddsa_verify composes them.  Header-only and free of device code, so tests/cpp/builder_host.hip compiles it alone under the sanitizers.
 #pragma once
 #include <array>
 #include <map>
 #include "circuit.hpp"
 #include "babyjub.hpp"
 #include "poseidon.hpp"
+#include "eddsa.hpp"
 
 struct zk_builder {
     struct Term { zk::Fr w; uint32_t wire; };
@@ -144,6 +145,10 @@ struct BuilderOps {
     uint32_t poseidon_forms(const Form* in, size_t arity) {
         const PoseidonParams* p = poseidon_params(arity);
         if (!p) fail("poseidon: the arity must be 1, 2 or 4, got " + std::to_string(arity));
+        return poseidon_forms_over(in, p);
+    }
+    // over any parameter set: width 6 (poseidon_params_t6) reaches the builder through eddsa_verify only
+    uint32_t poseidon_forms_over(const Form* in, const PoseidonParams* p) {
         const unsigned t = p->t;
         Form state[POSEIDON_MAX_T], next[POSEIDON_MAX_T];
         for (unsigned i = 1; i < t; ++i) state[i] = in[i - 1];
@@ -344,6 +349,51 @@ struct BuilderOps {
             select(bit[i]);
             babyjub_add_forms(form_of(d[0]), form_of(d[1]), form_of(d[2]), x2, y2, nullptr, out);
             for (int k = 0; k < 3; ++k) acc[k] = form_of(out[k]);
+        }
+    }
+
+    // ---- EdDSA-Poseidon (eddsa.hpp): [S] Base8 = R8 + [8] ([hm] A) with hm = H6(R8, A, M), from the gadgets above ----
+    static constexpr size_t EDDSA_S_BITS = 251, EDDSA_HM_BITS = 254;
+    // bits < bound through the comparator against constant wires, the result pinned to 1
+    void assert_below(const uint32_t* bits, size_t n, const uint64_t* bound) {
+        std::vector<uint32_t> k(n);
+        for (size_t i = 0; i < n; ++i) k[i] = (uint32_t)((bound[i / 64] >> (i % 64)) & 1);   // ZK_WIRE_ONE or ZK_WIRE_ZERO
+        const uint32_t lt = compare(ZK_CMP_LESS, bits, k.data(), n);
+        assert_forms(form_sum(form_of(lt), form_const(Fr::one()), -Fr::one()), form_of(1));
+    }
+    // In this order: R8 on the curve; S < l; hm < r (circomlib's alias check: without it hm + r passes where it is below 2^254); the
+    // digest; (sum 2^i hm_bits[i] - digest) * 1 = 0; [hm] A, which asserts A on the curve and every hm bit; three doublings; + R8;
+    // [S] Base8, which asserts every S bit; and per coordinate X1 Z2 = t1, X2 Z1 = t2, (t1 - t2) * 1 = 0.
+    void eddsa_verify(const uint32_t a_xy[2], const uint32_t r8_xy[2], uint32_t msg, const uint32_t* s_bits, const uint32_t* hm_bits) {
+        known(a_xy[0]); known(a_xy[1]); known(r8_xy[0]); known(r8_xy[1]); known(msg);
+        for (size_t i = 0; i < EDDSA_S_BITS; ++i) known(s_bits[i]);
+        for (size_t i = 0; i < EDDSA_HM_BITS; ++i) known(hm_bits[i]);
+        const Fr minus = -Fr::one();
+        babyjub_assert_on_curve(r8_xy[0], r8_xy[1]);
+        uint64_t r[4];
+        for (int i = 0; i < 4; ++i) r[i] = (uint64_t)FrParams::P[2 * i] | ((uint64_t)FrParams::P[2 * i + 1] << 32);
+        assert_below(s_bits, EDDSA_S_BITS, BABYJUB_ORDER);
+        assert_below(hm_bits, EDDSA_HM_BITS, r);
+        const Form in[5] = {form_of(r8_xy[0]), form_of(r8_xy[1]), form_of(a_xy[0]), form_of(a_xy[1]), form_of(msg)};
+        const uint32_t digest = poseidon_forms_over(in, &poseidon_params_t6());
+        Form sum;
+        for (size_t i = 0; i < EDDSA_HM_BITS; ++i) {
+            uint64_t w[4] = {0, 0, 0, 0};
+            w[i / 64] = 1ull << (i % 64);
+            form_add(sum, form_of(hm_bits[i]), Fr::from_canonical(fr_from_words(w)));
+        }
+        assert_forms(form_sum(sum, form_of(digest), minus), form_of(1));
+        uint32_t p[3], q[3], left[3];
+        babyjub_mul(a_xy, hm_bits, EDDSA_HM_BITS, p);
+        for (int k = 0; k < 3; ++k) {
+            babyjub_dbl_forms(form_of(p[0]), form_of(p[1]), form_of(p[2]), q);
+            std::copy(q, q + 3, p);
+        }
+        babyjub_add_forms(form_of(p[0]), form_of(p[1]), form_of(p[2]), form_of(r8_xy[0]), form_of(r8_xy[1]), nullptr, q);
+        babyjub_mul_fixed(s_bits, EDDSA_S_BITS, left);
+        for (int k = 0; k < 2; ++k) {
+            const Form t1 = form_of(sub_forms(form_of(left[k]), form_of(q[2]))), t2 = form_of(sub_forms(form_of(q[k]), form_of(left[2])));
+            assert_forms(form_sum(t1, t2, minus), form_of(1));
         }
     }
 

@@ -109,7 +109,8 @@ struct ProveState;    // prove.hip
 struct VerifyBatchState;   // verify_batch.hip
 struct QapCheckState;      // qap_check.hip
 struct PoseidonState;      // poseidon.hip
-struct BabyjubState;       // babyjub.hip
+struct BabyjubState;       // babyjub_dev.cuh
+struct EddsaState;         // eddsa.hip
 
 }  // namespace zk
 
@@ -124,6 +125,7 @@ struct zk_ctx {
     std::shared_ptr<zk::QapCheckState> qap_check;         // zk_qap_check*: its stream and buffers
     std::shared_ptr<zk::PoseidonState> poseidon;          // zk_poseidon_*: the device copy of the parameters, uploaded once per arity
     std::shared_ptr<zk::BabyjubState> babyjub;            // zk_babyjub_mul_batch: the window table of Base8, uploaded once, and the flags
+    std::shared_ptr<zk::EddsaState> eddsa;                // zk_eddsa_verify_batch: the width-6 Poseidon parameters, uploaded once, and the challenges
     hipEvent_t submit_wait_evt = nullptr;  // consumed by the next prove_submit / prove_msm_submit: its first kernels wait for this event (comm.hip)
     int cur_slot = -1;
     std::string last_error;

@@ -10,7 +10,11 @@
 // then x_0..x_{t-1}, y_0..y_{t-1} are 2t more, each reduced mod r and all redrawn if two are equal or some x_i + y_j = 0, and
 // M[i][j] = 1 / (x_i + y_j).  The paper's script also redraws M when a security test fails; for these three widths the first draw is
 // the published one (tests/test_poseidon.py holds C, M and digests against the published values), which is why no other width is
-// offered.  Header-only and free of device code: tests/cpp/poseidon_host.hip compiles it alone under the sanitizers.
+// offered.  Width 6 (five inputs, R_P = 60) is the EdDSA challenge hash of eddsa.hpp and is INTERNAL: poseidon_params_t6() hands it to
+// zk_eddsa_*, the gadget of zk_builder_eddsa_verify and eddsa.hip, while poseidon_rp(), which gates the public calls, still answers
+// 0 for arity 5.  Its first draw gives hash(1, 2, 3, 4, 5) = 0x0dab9449...eeb123c0, the digest circomlibjs and go-iden3-crypto publish
+// (tests/test_eddsa.py), so the first draw is the published one for this width too.
+// Header-only and free of device code: tests/cpp/poseidon_host.hip compiles it alone under the sanitizers.
 #pragma once
 #include <memory>
 #include <mutex>
@@ -20,7 +24,8 @@
 namespace zk {
 
 constexpr unsigned POSEIDON_RF = 8;
-constexpr unsigned POSEIDON_MAX_T = 5;
+constexpr unsigned POSEIDON_MAX_T = 6;
+constexpr unsigned POSEIDON_RP_T6 = 60;
 // 0: the arity is not offered
 static inline unsigned poseidon_rp(size_t arity) { return arity == 1 ? 56 : arity == 2 ? 57 : arity == 4 ? 60 : 0; }
 
@@ -65,10 +70,10 @@ struct PoseidonGrain {
     }
 };
 
-static inline PoseidonParams poseidon_generate(size_t arity) {
+static inline PoseidonParams poseidon_generate(size_t arity, unsigned rp) {
     PoseidonParams p;
     p.t = (unsigned)arity + 1;
-    p.rp = poseidon_rp(arity);
+    p.rp = rp;
     const unsigned t = p.t;
     PoseidonGrain g(t, p.rf, p.rp);
     while (p.c.size() < (size_t)p.rounds() * t) {
@@ -97,8 +102,14 @@ inline const PoseidonParams* poseidon_params(size_t arity) {
     static std::unique_ptr<PoseidonParams> made[POSEIDON_MAX_T];
     if (!poseidon_rp(arity)) return nullptr;
     std::lock_guard<std::mutex> lock(mu);
-    if (!made[arity]) made[arity].reset(new PoseidonParams(poseidon_generate(arity)));
+    if (!made[arity]) made[arity].reset(new PoseidonParams(poseidon_generate(arity, poseidon_rp(arity))));
     return made[arity].get();
+}
+
+// width 6, for eddsa.hpp and the EdDSA gadget only
+inline const PoseidonParams& poseidon_params_t6() {
+    static const PoseidonParams made = poseidon_generate(5, POSEIDON_RP_T6);
+    return made;
 }
 
 static inline Fr poseidon_pow5(const Fr& x) {
