@@ -229,6 +229,8 @@ extern "C" {
     fn zk_eddsa_verify(a: *const u64, msg: *const u64, r8: *const u64, s: *const u64, status: *mut c_int) -> c_int;
     fn zk_eddsa_verify_batch(ctx: *mut ZkCtx, d_points_msg: *const c_void, d_s: *const c_void, count: usize, d_status: *mut c_void,
                              d_bits_out: *mut c_void, bits_stride_bytes: usize) -> c_int;
+    fn zk_eddsa_sign_batch(ctx: *mut ZkCtx, d_keys: *const c_void, d_nonce_keys: *const c_void, d_msgs: *const c_void, count: usize,
+                           d_points_msg_out: *mut c_void, d_s_out: *mut c_void, d_bits_out: *mut c_void, bits_stride_bytes: usize) -> c_int;
     // Poseidon over Fr (circomlib's parameter sets): host hash, GPU batch hashing, a device-resident Merkle tree and its paths
     fn zk_poseidon_hash(inputs: *const u64, arity: usize, out: *mut u64) -> c_int;
     fn zk_poseidon_params(arity: usize, rf: *mut c_uint, rp: *mut c_uint, round_constants: *mut u64, mds: *mut u64) -> c_int;
@@ -1568,6 +1570,13 @@ pub fn eddsa_verify(a: &[u64; 8], msg: &[u64; 4], r8: &[u64; 8], s: &[u64; 4]) -
 pub fn eddsa_verify_batch(ctx: *mut ZkCtx, d_points_msg: *const c_void, d_s: *const c_void, count: usize, d_status: *mut c_void,
                           d_bits_out: *mut c_void, bits_stride_bytes: usize) {
     unsafe { check(ctx, zk_eddsa_verify_batch(ctx, d_points_msg, d_s, count, d_status, d_bits_out, bits_stride_bytes)) }
+}
+/// zk_eddsa_sign_batch: `count` signatures, device to device; d_keys, d_nonce_keys, d_msgs: count x 4 words (0 < k < l, n < r, M < r);
+/// d_points_msg_out: count x 20 words (A.x, A.y, R8.x, R8.y, M) with A = [k] Base8 computed in the call, d_s_out: count x 4; d_bits_out
+/// null, or the rows eddsa_verify_batch writes.  An input out of range refuses the call before anything is written
+pub fn eddsa_sign_batch(ctx: *mut ZkCtx, d_keys: *const c_void, d_nonce_keys: *const c_void, d_msgs: *const c_void, count: usize,
+                        d_points_msg_out: *mut c_void, d_s_out: *mut c_void, d_bits_out: *mut c_void, bits_stride_bytes: usize) {
+    unsafe { check(ctx, zk_eddsa_sign_batch(ctx, d_keys, d_nonce_keys, d_msgs, count, d_points_msg_out, d_s_out, d_bits_out, bits_stride_bytes)) }
 }
 
 /// zk_poseidon_tree_*: a binary Merkle tree over Poseidon of arity 2 that stays on the device; paths() writes leaf | siblings and the

@@ -700,6 +700,29 @@ int zk_eddsa_verify(const uint64_t a[8], const uint64_t msg[4], const uint64_t r
  * Per-signature defects are statuses and never refuse the call. */
 int zk_eddsa_verify_batch(zk_ctx* ctx, const void* d_points_msg, const void* d_s, size_t count, void* d_status, void* d_bits_out,
                           size_t bits_stride_bytes);
+/* `count` signatures on the GPU, one per lane: instance j is signed exactly as zk_eddsa_sign(k_j, n_j, M_j) signs it (the scheme
+ * above).  d_keys, d_nonce_keys, d_msgs: count x 4 words each, k, n and M of instance j.  d_points_msg_out: count x 20 words,
+ * (A.x, A.y, R8.x, R8.y, M) per instance -- d_points_msg of zk_eddsa_verify_batch and d_in_fields of the gadget's circuit.  A = [k] Base8
+ * is computed in the call and never taken from the caller: signing under a public key that is not the key's own leaks k.  d_s_out:
+ * count x 4 words, S -- d_s of zk_eddsa_verify_batch.  d_bits_out may be NULL; otherwise row j, at d_bits_out + j *
+ * bits_stride_bytes, receives the 64 bytes zk_eddsa_verify_batch writes there: the 251 bits of S, then the 254 bits of hm as the full
+ * integer below r, least significant first, then 7 zero bits; bytes of a row past the 64th are not written.  With it the chain
+ * zk_eddsa_sign_batch -> zk_mixgen_run -> zk_prove_batch_submit runs with no verify call and no host step.  Every word written equals
+ * what zk_eddsa_public_key, zk_eddsa_sign and zk_eddsa_challenge give on the host.
+ * Three launches: the range checks with rho = H6(n, M, 0, 0, 0) mod l; A and R8 by two walks over the table of zk_babyjub_mul_batch
+ * and ONE Fermat inversion for both; hm = H6(R8, A, M) and S = (rho + 8 (hm mod l) k) mod l (arithmetic mod l: csrc/eddsa_modl.hpp).
+ * No LDS.  Secrets: rho lives in a context buffer (32 bytes an instance) between the launches; the last launch that reads it
+ * overwrites it with zeros, and a refused call wipes what it wrote there.  k is read from the caller's array and kept nowhere else.
+ * The instruction stream is the same in every lane whatever the data -- no lane returns early, no loop bound or branch depends on
+ * a secret -- but, as in the fixed-base kernel of zk_babyjub_mul_batch, the table entry is addressed by four bits of a secret scalar
+ * (k, then rho): the addresses a lane reads depend on its secrets.
+ * All device pointers, 8-byte aligned.  Complete on return.  count == 0: ZK_OK, nothing touched.  Refusals are those of
+ * zk_babyjub_mul_batch, not statuses: a bad secret key is the caller's error, not a verdict.  ZK_ERR_ARG with text: a null or
+ * misaligned pointer; with d_bits_out, a stride below 64 or no multiple of 8.  ZK_ERR_RANGE, found on the device BEFORE anything is
+ * written to the three outputs, the text naming the LOWEST such instance and which input it is -- within one instance the key, then
+ * the nonce key, then the message: k == 0, k >= l, n >= r, M >= r. */
+int zk_eddsa_sign_batch(zk_ctx* ctx, const void* d_keys, const void* d_nonce_keys, const void* d_msgs, size_t count,
+                        void* d_points_msg_out, void* d_s_out, void* d_bits_out, size_t bits_stride_bytes);
 
 /* ------------------------------------------------------------------------------------------
  * CRS  (SigmaG1 / SigmaG2, groth16/mod.rs:105-121)

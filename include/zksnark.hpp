@@ -610,6 +610,15 @@ inline void verify_batch(const Context& c, const void* d_points_msg, const void*
                          size_t bits_stride_bytes = 64) {
     c.check(zk_eddsa_verify_batch(c.get(), d_points_msg, d_s, count, d_status, d_bits_out, bits_stride_bytes), "eddsa::verify_batch");
 }
+// d_keys, d_nonce_keys, d_msgs: count x 4 words each (0 < k < l, n < r, M < r); instance j is signed as sign(k_j, n_j, M_j).
+// d_points_msg_out: count x 20 words (A.x, A.y, R8.x, R8.y, M), A = [k] Base8 computed in the call; d_s_out: count x 4 words -- the
+// inputs of verify_batch; d_bits_out: nullptr, or the rows verify_batch writes; device pointers.  An input out of range throws
+// (ZK_ERR_RANGE, the text naming the lowest instance and the input) before anything is written
+inline void sign_batch(const Context& c, const void* d_keys, const void* d_nonce_keys, const void* d_msgs, size_t count, void* d_points_msg_out,
+                       void* d_s_out, void* d_bits_out = nullptr, size_t bits_stride_bytes = 64) {
+    c.check(zk_eddsa_sign_batch(c.get(), d_keys, d_nonce_keys, d_msgs, count, d_points_msg_out, d_s_out, d_bits_out, bits_stride_bytes),
+            "eddsa::sign_batch");
+}
 }  // namespace eddsa
 
 // zk_poseidon_tree_*: a binary Merkle tree over Poseidon of arity 2 that stays on the device; paths() writes leaf | siblings and the

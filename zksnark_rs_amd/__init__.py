@@ -1134,6 +1134,44 @@ class Context:
         status = d_status.cpu().numpy().view(np.uint32)[:n]
         return (status, d_bits.cpu().numpy()[:n]) if bits else status
 
+    def eddsa_sign_batch(self, keys, nonce_keys, msgs, count=None, d_points_msg_ptr=None, d_s_ptr=None, d_bits_ptr=None, bits_stride_bytes=64,
+                         bits=False):
+        """zk_eddsa_sign_batch: instance j is signed as eddsa.sign(keys[j], nonce_keys[j], msgs[j]).  Device form (count, d_points_msg_ptr
+        and d_s_ptr given): keys, nonce_keys and msgs are device pointers to count x 4 words each; the rows (A.x, A.y, R8.x, R8.y, M), with
+        A = [k] Base8 computed in the call, go to count x 20 words at d_points_msg_ptr, S to count x 4 words at d_s_ptr -- the inputs of
+        eddsa_verify_batch -- and, where d_bits_ptr is given, the bit rows eddsa_verify_batch writes to rows bits_stride_bytes apart.
+        Host form: keys, nonce_keys, msgs = integers or (count, 4) uint64 -> ((count, 5, 4), (count, 4)) uint64, plus
+        (count, bits_stride_bytes) uint8 with bits=True, staged through torch tensors on the context's device.  An input out of range
+        raises ZkError (ZK_ERR_RANGE, the text naming the lowest instance and the input) before anything is written."""
+        if d_points_msg_ptr is not None:
+            self._check(self.lib.zk_eddsa_sign_batch(self.ptr, C.c_void_p(keys), C.c_void_p(nonce_keys), C.c_void_p(msgs), count,
+                                                     C.c_void_p(d_points_msg_ptr), C.c_void_p(d_s_ptr),
+                                                     C.c_void_p(d_bits_ptr) if d_bits_ptr is not None else None, bits_stride_bytes))
+            return None
+        import torch
+        from .babyjub import scalars_to_words
+        words = [np.ascontiguousarray(a if isinstance(a, np.ndarray) else scalars_to_words(a), dtype=np.uint64).reshape(-1, 4)
+                 for a in (keys, nonce_keys, msgs)]
+        n = words[0].shape[0]
+        if words[1].shape[0] != n or words[2].shape[0] != n:
+            raise ZkError(_lib.ZK_ERR_ARG, "eddsa: %d keys, %d nonce keys and %d messages" % tuple(w.shape[0] for w in words))
+        dev = "cuda:%d" % self.device
+        d_k, d_n, d_m = [torch.from_numpy(np.ascontiguousarray(np.vstack([w, np.zeros((1, 4), np.uint64)])).view(np.int64)).to(dev)
+                         for w in words]                     # never an empty tensor
+        d_p = torch.zeros((n + 1, 20), dtype=torch.int64, device=dev)
+        d_s = torch.zeros((n + 1, 4), dtype=torch.int64, device=dev)
+        d_bits = torch.zeros((n + 1, bits_stride_bytes), dtype=torch.uint8, device=dev) if bits else None
+        torch.cuda.synchronize(dev)
+        try:
+            self._check(self.lib.zk_eddsa_sign_batch(self.ptr, C.c_void_p(d_k.data_ptr()), C.c_void_p(d_n.data_ptr()), C.c_void_p(d_m.data_ptr()), n,
+                                                     C.c_void_p(d_p.data_ptr()), C.c_void_p(d_s.data_ptr()),
+                                                     C.c_void_p(d_bits.data_ptr()) if bits else None, bits_stride_bytes))
+        finally:
+            d_k.zero_()                                     # the staged copy of the keys
+            torch.cuda.synchronize(dev)
+        out = (d_p.cpu().numpy().view(np.uint64)[:n].reshape(n, 5, 4), d_s.cpu().numpy().view(np.uint64)[:n])
+        return out + (d_bits.cpu().numpy()[:n],) if bits else out
+
     # ---- profiling ----
     def profile_reset(self):
         self._check(self.lib.zk_profile_reset(self.ptr))

@@ -222,6 +222,7 @@ SIGNATURES = {
     "zk_eddsa_sign": (C.c_int, [u64p, u64p, u64p, u64p, u64p]),
     "zk_eddsa_verify": (C.c_int, [u64p, u64p, u64p, u64p, C.POINTER(C.c_int)]),
     "zk_eddsa_verify_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "zk_eddsa_sign_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "zk_msm_auto_window": (C.c_int, [C.c_size_t]),
     "zk_msm_auto_window_g2": (C.c_int, [C.c_size_t]),
     "zk_circuit_qap": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),

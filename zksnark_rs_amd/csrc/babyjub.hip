@@ -19,28 +19,6 @@ namespace zk {
 
 static constexpr unsigned long long BABYJUB_NO_ERROR = ~0ull;
 
-__device__ __forceinline__ void bj_store(const Fr& v, uint64_t* __restrict__ w) {
-    const Fr c = v.to_canonical();
-#pragma unroll
-    for (int i = 0; i < 4; ++i) w[i] = (uint64_t)c.l[2 * i] | ((uint64_t)c.l[2 * i + 1] << 32);
-}
-// x^(r - 2): the exponent is the same in every lane and is shifted through scalar registers, so the branch is uniform
-__device__ __forceinline__ Fr bj_inv(const Fr& x) {
-    uint32_t e[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) e[i] = FrParams::P[i];
-    e[0] -= 2;
-    Fr acc = Fr::one();
-#pragma unroll 1
-    for (int i = 0; i < 256; ++i) {
-        acc = acc.sqr();
-        if (e[7] >> 31) acc = acc * x;
-#pragma unroll
-        for (int w = 7; w > 0; --w) e[w] = (e[w] << 1) | (e[w - 1] >> 31);
-        e[0] <<= 1;
-    }
-    return acc;
-}
 __device__ __forceinline__ void bj_store_affine(const BjPoint& p, uint64_t* __restrict__ out) {
     const Fr zi = bj_inv(p.Z);
     bj_store(p.X * zi, out);
@@ -55,16 +33,7 @@ k_babyjub_mul_fixed(const BjAffine* __restrict__ table, BjConsts k, const uint64
     if (j >= count) return;
     uint32_t s[8];
     bj_load_words(scalars + 4 * j, s);
-    BjPoint acc = BjPoint::identity();
-#pragma unroll 1
-    for (unsigned w = 0; w < BABYJUB_FIXED_WINDOWS; ++w) {
-        const BjAffine e = table[w * (1u << BABYJUB_FIXED_WINDOW) + (s[0] & 15)];
-#pragma unroll
-        for (int i = 0; i < 7; ++i) s[i] = (s[i] >> 4) | (s[i + 1] << 28);
-        s[7] >>= 4;
-        if (w == 0) { acc.X = e.x; acc.Y = e.y; }          // the first window is the accumulator itself (w is uniform)
-        else acc = bj_add_mixed(k, acc, e.x, e.y);
-    }
+    const BjPoint acc = bj_mul_fixed(table, k, s);
     bj_store_affine(acc, out + j * out_stride);
 }
 

@@ -1,5 +1,6 @@
 // babyjub_dev.cuh -- what babyjub.hip and eddsa.hip share on the device: the per-context state with the window table of Base8, the
-// loads of canonical words and the selection among four register entries.
+// loads and stores of canonical words, the fixed-base walk over the table, the Fermat inversion and the selection among four register
+// entries.
 #pragma once
 #include "common.hpp"
 #include "babyjub.hpp"
@@ -32,6 +33,42 @@ __device__ __forceinline__ Fr bj_load_raw(const uint64_t* __restrict__ w) {
     Fr x;
     bj_load_words(w, x.l);
     return x;
+}
+__device__ __forceinline__ void bj_store(const Fr& v, uint64_t* __restrict__ w) {
+    const Fr c = v.to_canonical();
+#pragma unroll
+    for (int i = 0; i < 4; ++i) w[i] = (uint64_t)c.l[2 * i] | ((uint64_t)c.l[2 * i + 1] << 32);
+}
+// x^(r - 2): the exponent is the same in every lane and is shifted through scalar registers, so the branch is uniform
+__device__ __forceinline__ Fr bj_inv(const Fr& x) {
+    uint32_t e[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) e[i] = FrParams::P[i];
+    e[0] -= 2;
+    Fr acc = Fr::one();
+#pragma unroll 1
+    for (int i = 0; i < 256; ++i) {
+        acc = acc.sqr();
+        if (e[7] >> 31) acc = acc * x;
+#pragma unroll
+        for (int w = 7; w > 0; --w) e[w] = (e[w] << 1) | (e[w - 1] >> 31);
+        e[0] <<= 1;
+    }
+    return acc;
+}
+// [s] Base8 over the context's table, from the least significant window of 4 bits: 63 mixed additions, no doubling.  s is consumed.
+__device__ __forceinline__ BjPoint bj_mul_fixed(const BjAffine* __restrict__ table, const BjConsts& k, uint32_t (&s)[8]) {
+    BjPoint acc = BjPoint::identity();
+#pragma unroll 1
+    for (unsigned w = 0; w < BABYJUB_FIXED_WINDOWS; ++w) {
+        const BjAffine e = table[w * (1u << BABYJUB_FIXED_WINDOW) + (s[0] & 15)];
+#pragma unroll
+        for (int i = 0; i < 7; ++i) s[i] = (s[i] >> 4) | (s[i + 1] << 28);
+        s[7] >>= 4;
+        if (w == 0) { acc.X = e.x; acc.Y = e.y; }          // the first window is the accumulator itself (w is uniform)
+        else acc = bj_add_mixed(k, acc, e.x, e.y);
+    }
+    return acc;
 }
 __device__ __forceinline__ Fr bj_pick(unsigned digit, const Fr& e0, const Fr& e1, const Fr& e2, const Fr& e3) {
     Fr o;

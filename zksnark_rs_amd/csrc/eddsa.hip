@@ -1,5 +1,5 @@
-// eddsa.hip -- EdDSA-Poseidon (eddsa.hpp) on the device: zk_eddsa_verify_batch, one signature per lane, a verdict per signature and no
-// affine point, so nothing is inverted.  Two launches:
+// eddsa.hip -- EdDSA-Poseidon (eddsa.hpp) on the device: zk_eddsa_verify_batch and, below, zk_eddsa_sign_batch.  Verification: one
+// signature per lane, a verdict per signature and no affine point, so nothing is inverted.  Two launches:
 //   k_eddsa_challenge   the checks that need no curve arithmetic -- a word pattern >= r, A and R8 on the curve, S < l -- folded into a
 //                       status word (the lowest code wins); hm = H6(R8.x, R8.y, A.x, A.y, M) by the permutation of width 6, the state of
 //                       six elements in registers, M times the state one row at a time, the constants read at indices that are the
@@ -13,9 +13,23 @@
 // instruction stream whatever its data: no lane returns early on a defect, a lane with a point off the curve walks the formulas on
 // whatever values come out -- all of it register arithmetic, the table index is four bits of S -- and nothing depends on its Z being
 // non-zero, since its status is already set.
+//
+// zk_eddsa_sign_batch, one instance (k, n, M) per lane, three launches:
+//   k_eddsa_sign_nonce      the range checks (0 < k < l, n < r, M < r), the lowest offender recorded by atomicMin, and
+//                           rho = H6(n, M, 0, 0, 0) mod l into a context buffer.  The host reads the flag and refuses before any launch
+//                           that writes an output.
+//   k_eddsa_sign_points     A = [k] Base8 and R8 = [rho] Base8 by the walk of k_babyjub_mul_fixed, ONE Fermat inversion of Z_A Z_R for
+//                           both, the row (A.x, A.y, R8.x, R8.y, M).
+//   k_eddsa_sign_response   hm = H6 over the row by the permutation of k_eddsa_challenge, S = (rho + 8 (hm mod l) k) mod l by
+//                           eddsa_modl.hpp, S and the bit row; zeros over rho.
+// The first launch stands alone because the checks must be complete before an output is written.  The other two would fit one kernel
+// (184 VGPRs, no scratch) and are split all the same: the response kernel runs at 166 VGPRs, three waves a SIMD, the fused form at two,
+// and measured 1 % slower at 2^20 instances (DESIGN 4s has the figures).  rho lives in the context buffer between the launches only;
+// k is read from the caller's array by each launch and kept nowhere.
 #include <utility>
 #include "babyjub_dev.cuh"
 #include "eddsa.hpp"
+#include "eddsa_modl.hpp"
 
 namespace zk {
 
@@ -25,7 +39,10 @@ static constexpr unsigned EDDSA_POINT_WORDS = 20, EDDSA_BITS_WORDS = 8;   // wor
 struct EddsaState {
     DevBuf<Fr> par;            // C (EDDSA_ROUNDS x 6) then M (6 x 6, row-major), Montgomery form
     DevBuf<uint64_t> hm;       // count x 4 canonical words, grow-only
+    DevBuf<uint64_t> rho;      // signing: count x 4 words, grow-only; secret between the launches of a call, zero afterwards
+    DevBuf<unsigned long long> flag;   // signing: the lowest input out of range
 };
+static constexpr unsigned long long EDDSA_NO_ERROR = ~0ull;
 
 // s < l, by the borrow of s - l over limbs of 32 bits
 __device__ __forceinline__ bool eddsa_below_l(const uint32_t (&s)[8]) {
@@ -66,6 +83,30 @@ __device__ __forceinline__ void eddsa_round(Fr (&s)[EDDSA_T], const Fr* __restri
     ((s[I] = n[I]), ...);
 }
 
+// the permutation of width 6 over the state in registers; par: C (EDDSA_ROUNDS x 6) then M
+__device__ __forceinline__ void eddsa_permute(Fr (&s)[EDDSA_T], const Fr* __restrict__ par) {
+    const Fr* __restrict__ c = par;
+    const Fr* __restrict__ m = par + (size_t)EDDSA_ROUNDS * EDDSA_T;
+#pragma unroll 1
+    for (unsigned r = 0; r < POSEIDON_RF / 2; ++r, c += EDDSA_T) eddsa_round<true>(s, c, m, EddsaSeq<EDDSA_T>());
+#pragma unroll 1
+    for (unsigned r = 0; r < POSEIDON_RP_T6; ++r, c += EDDSA_T) eddsa_round<false>(s, c, m, EddsaSeq<EDDSA_T>());
+#pragma unroll 1
+    for (unsigned r = 0; r < POSEIDON_RF / 2; ++r, c += EDDSA_T) eddsa_round<true>(s, c, m, EddsaSeq<EDDSA_T>());
+}
+// a row of d_bits_out: 251 bits of S, then 254 bits of hm: 505 bits in 16 limbs; all zero where `range` is false
+__device__ __forceinline__ void eddsa_store_bits(uint64_t* __restrict__ row, const uint32_t (&sig)[8], const uint32_t (&hm)[8], bool range) {
+    uint32_t w[16];
+#pragma unroll
+    for (int i = 0; i < 7; ++i) w[i] = sig[i];
+    w[7] = (sig[7] & 0x07ffffffu) | (hm[0] << 27);
+#pragma unroll
+    for (int i = 0; i < 7; ++i) w[8 + i] = (hm[i] >> 5) | (hm[i + 1] << 27);
+    w[15] = hm[7] >> 5;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) row[i] = range ? (uint64_t)w[2 * i] | ((uint64_t)w[2 * i + 1] << 32) : 0;
+}
+
 // grid: ceil(count / BABYJUB_BLOCK) blocks, lane j owns signature j.  bits: nullptr, or rows of bits_stride words of 64 bits.
 __global__ void __launch_bounds__(BABYJUB_BLOCK)
 k_eddsa_challenge(const Fr* __restrict__ par, BjConsts k, const uint64_t* __restrict__ points, const uint64_t* __restrict__ sigs, size_t count,
@@ -88,30 +129,11 @@ k_eddsa_challenge(const Fr* __restrict__ par, BjConsts k, const uint64_t* __rest
     st = range ? st : ZK_EDDSA_RANGE;
     status[j] = st;
 
-    const Fr* __restrict__ c = par;
-    const Fr* __restrict__ m = par + (size_t)EDDSA_ROUNDS * EDDSA_T;
-#pragma unroll 1
-    for (unsigned r = 0; r < POSEIDON_RF / 2; ++r, c += EDDSA_T) eddsa_round<true>(s, c, m, EddsaSeq<EDDSA_T>());
-#pragma unroll 1
-    for (unsigned r = 0; r < POSEIDON_RP_T6; ++r, c += EDDSA_T) eddsa_round<false>(s, c, m, EddsaSeq<EDDSA_T>());
-#pragma unroll 1
-    for (unsigned r = 0; r < POSEIDON_RF / 2; ++r, c += EDDSA_T) eddsa_round<true>(s, c, m, EddsaSeq<EDDSA_T>());
+    eddsa_permute(s, par);
     const Fr d = s[0].to_canonical();
 #pragma unroll
     for (int i = 0; i < 4; ++i) hm_out[4 * j + i] = (uint64_t)d.l[2 * i] | ((uint64_t)d.l[2 * i + 1] << 32);
-    if (bits) {
-        // 251 bits of S, then 254 bits of hm: 505 bits in 16 limbs, all zero for a word pattern >= r
-        uint32_t w[16];
-#pragma unroll
-        for (int i = 0; i < 7; ++i) w[i] = sig.l[i];
-        w[7] = (sig.l[7] & 0x07ffffffu) | (d.l[0] << 27);
-#pragma unroll
-        for (int i = 0; i < 7; ++i) w[8 + i] = (d.l[i] >> 5) | (d.l[i + 1] << 27);
-        w[15] = d.l[7] >> 5;
-        uint64_t* __restrict__ row = bits + j * bits_stride;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) row[i] = range ? (uint64_t)w[2 * i] | ((uint64_t)w[2 * i + 1] << 32) : 0;
-    }
+    if (bits) eddsa_store_bits(bits + j * bits_stride, sig.l, d.l, range);   // all zero for a word pattern >= r
 }
 
 // grid as above.  status: what k_eddsa_challenge wrote; VALID becomes the verdict of the equation.
@@ -146,19 +168,83 @@ k_eddsa_curve(const BjAffine* __restrict__ table, BjConsts k, const uint64_t* __
     right = bj_dbl(k, bj_dbl(k, bj_dbl(k, right)));                       // [8] ([hm] A): 8 hm is never a scalar
     right = bj_add_mixed(k, right, Fr::from_canonical(bj_load_raw(in + 8)), Fr::from_canonical(bj_load_raw(in + 12)));
     bj_load_words(sigs + 4 * j, s);
-    BjPoint left = BjPoint::identity();
-#pragma unroll 1
-    for (unsigned w = 0; w < BABYJUB_FIXED_WINDOWS; ++w) {
-        const BjAffine e = table[w * (1u << BABYJUB_FIXED_WINDOW) + (s[0] & 15)];
-#pragma unroll
-        for (int i = 0; i < 7; ++i) s[i] = (s[i] >> 4) | (s[i + 1] << 28);
-        s[7] >>= 4;
-        if (w == 0) { left.X = e.x; left.Y = e.y; }                       // the first window is the accumulator itself (w is uniform)
-        else left = bj_add_mixed(k, left, e.x, e.y);
-    }
+    const BjPoint left = bj_mul_fixed(table, k, s);
     const bool equal = left.X * right.Z == right.X * left.Z && left.Y * right.Z == right.Y * left.Z;
     const uint32_t before = status[j];
     status[j] = before != ZK_EDDSA_VALID ? before : equal ? ZK_EDDSA_VALID : ZK_EDDSA_MISMATCH;
+}
+
+// ---- zk_eddsa_sign_batch: lane j signs instance j ------------------------------------------------------------------------------
+// flag: the lowest 4 j + input (0 the key, 1 the nonce key, 2 the message) out of range, by atomicMin; rho_out: H6(n, M, 0, 0, 0) mod l.
+// Nothing else is written.  Reporting a refusal is the only branch on an input, and the caller is told of it anyway.
+__global__ void __launch_bounds__(BABYJUB_BLOCK)
+k_eddsa_sign_nonce(const Fr* __restrict__ par, const uint64_t* __restrict__ keys, const uint64_t* __restrict__ nonce_keys,
+                   const uint64_t* __restrict__ msgs, size_t count, uint64_t* __restrict__ rho_out, unsigned long long* __restrict__ flag) {
+    const size_t j = (size_t)blockIdx.x * BABYJUB_BLOCK + threadIdx.x;
+    if (j >= count) return;
+    uint32_t key[8];
+    bj_load_words(keys + 4 * j, key);
+    const Fr n = bj_load_raw(nonce_keys + 4 * j), msg = bj_load_raw(msgs + 4 * j);
+    const bool key_ok = ((key[0] | key[1] | key[2] | key[3] | key[4] | key[5] | key[6] | key[7]) != 0) & eddsa_below_l(key);
+    const unsigned bad = !key_ok ? 0u : !n.raw_in_range() ? 1u : !msg.raw_in_range() ? 2u : 3u;
+    if (bad != 3u) atomicMin(flag, 4ull * j + bad);
+    Fr s[EDDSA_T];
+    s[0] = Fr::zero();
+    s[1] = Fr::from_canonical(n); s[2] = Fr::from_canonical(msg);
+    s[3] = Fr::zero(); s[4] = Fr::zero(); s[5] = Fr::zero();
+    eddsa_permute(s, par);
+    Fr d = s[0].to_canonical();
+    modl_reduce_r(d.l);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) rho_out[4 * j + i] = (uint64_t)d.l[2 * i] | ((uint64_t)d.l[2 * i + 1] << 32);
+}
+
+// A = [k] Base8 and R8 = [rho] Base8 by the walk of k_babyjub_mul_fixed, both to affine with one inversion, of Z_A Z_R; writes the
+// row (A.x, A.y, R8.x, R8.y, M).  The stream is the same in every lane; the table entry is addressed by four bits of k, then of rho.
+__global__ void __launch_bounds__(BABYJUB_BLOCK)
+k_eddsa_sign_points(const BjAffine* __restrict__ table, BjConsts k, const uint64_t* __restrict__ keys, const uint64_t* __restrict__ rho,
+                    const uint64_t* __restrict__ msgs, size_t count, uint64_t* __restrict__ points_out) {
+    const size_t j = (size_t)blockIdx.x * BABYJUB_BLOCK + threadIdx.x;
+    if (j >= count) return;
+    uint32_t s[8];
+    bj_load_words(keys + 4 * j, s);
+    const BjPoint a = bj_mul_fixed(table, k, s);
+    bj_load_words(rho + 4 * j, s);
+    const BjPoint r8 = bj_mul_fixed(table, k, s);
+    const Fr zi = bj_inv(a.Z * r8.Z), za = zi * r8.Z, zr = zi * a.Z;
+    uint64_t* __restrict__ out = points_out + EDDSA_POINT_WORDS * j;
+    bj_store(a.X * za, out);
+    bj_store(a.Y * za, out + 4);
+    bj_store(r8.X * zr, out + 8);
+    bj_store(r8.Y * zr, out + 12);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) out[16 + i] = msgs[4 * j + i];
+}
+
+// hm = H6 over the row just written, S = (rho + 8 (hm mod l) k) mod l; writes S and the bit row, and zeros over rho.
+__global__ void __launch_bounds__(BABYJUB_BLOCK)
+k_eddsa_sign_response(const Fr* __restrict__ par, const uint64_t* __restrict__ keys, uint64_t* __restrict__ rho, const uint64_t* __restrict__ points,
+                      size_t count, uint64_t* __restrict__ s_out, uint64_t* __restrict__ bits, size_t bits_stride) {
+    const size_t j = (size_t)blockIdx.x * BABYJUB_BLOCK + threadIdx.x;
+    if (j >= count) return;
+    const uint64_t* __restrict__ in = points + EDDSA_POINT_WORDS * j;
+    Fr s[EDDSA_T];
+    s[0] = Fr::zero();
+    s[1] = Fr::from_canonical(bj_load_raw(in + 8)); s[2] = Fr::from_canonical(bj_load_raw(in + 12));
+    s[3] = Fr::from_canonical(bj_load_raw(in)); s[4] = Fr::from_canonical(bj_load_raw(in + 4));
+    s[5] = Fr::from_canonical(bj_load_raw(in + 16));
+    eddsa_permute(s, par);
+    const Fr d = s[0].to_canonical();
+    uint32_t key[8], nonce[8], sig[8];
+    bj_load_words(keys + 4 * j, key);
+    bj_load_words(rho + 4 * j, nonce);
+    modl_response(nonce, d.l, key, sig);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        s_out[4 * j + i] = (uint64_t)sig[2 * i] | ((uint64_t)sig[2 * i + 1] << 32);
+        rho[4 * j + i] = 0;
+    }
+    if (bits) eddsa_store_bits(bits + j * bits_stride, sig, d.l, true);
 }
 
 static EddsaState& eddsa_state(zk_ctx* ctx) {
@@ -198,11 +284,68 @@ static void eddsa_verify_batch(zk_ctx* ctx, const uint64_t* d_points, const uint
     ctx->resolve_profile();
 }
 
+static void eddsa_sign_batch(zk_ctx* ctx, const uint64_t* d_keys, const uint64_t* d_nonce_keys, const uint64_t* d_msgs, size_t count,
+                             uint64_t* d_points, uint64_t* d_s, uint64_t* d_bits, size_t bits_stride_words) {
+    ZK_REQUIRE(count <= ((size_t)1 << 31) * BABYJUB_BLOCK, ZK_ERR_SIZE, "eddsa: too many signatures for one call");
+    EddsaState& st = eddsa_state(ctx);
+    const BjAffine* table = babyjub_table(ctx, babyjub_state(ctx));
+    st.rho.ensure(4 * count);
+    if (!st.flag.p) st.flag.alloc(1);
+    const dim3 grid(ceil_div(count, BABYJUB_BLOCK)), block(BABYJUB_BLOCK);
+    const BjConsts k = babyjub_consts();
+    unsigned long long bad = EDDSA_NO_ERROR;
+    ZK_HIP(hipMemcpyAsync(st.flag.p, &EDDSA_NO_ERROR, sizeof(bad), hipMemcpyHostToDevice, ctx->stream));
+    {
+        ProfScope ps(ctx, "eddsa_sign_nonce", (double)count * 128.0);
+        hipLaunchKernelGGL(k_eddsa_sign_nonce, grid, block, 0, ctx->stream, st.par.p, d_keys, d_nonce_keys, d_msgs, count, st.rho.p, st.flag.p);
+        ZK_HIP(hipGetLastError());
+    }
+    ZK_HIP(hipMemcpyAsync(&bad, st.flag.p, sizeof(bad), hipMemcpyDeviceToHost, ctx->stream));
+    ZK_HIP(hipStreamSynchronize(ctx->stream));
+    if (bad != EDDSA_NO_ERROR) {
+        ZK_HIP(hipMemsetAsync(st.rho.p, 0, 32 * count, ctx->stream));   // a refused call leaves no nonce behind
+        ZK_HIP(hipStreamSynchronize(ctx->stream));
+        ctx->resolve_profile();
+        const std::string at = " of instance " + std::to_string(bad / 4);
+        ZK_REQUIRE(bad % 4 != 0, ZK_ERR_RANGE, "eddsa: the key" + at + " is 0 or not below l");
+        ZK_REQUIRE(bad % 4 != 1, ZK_ERR_RANGE, "eddsa: the nonce key" + at + " is not below r");
+        ZK_REQUIRE(false, ZK_ERR_RANGE, "eddsa: the message" + at + " is not below r");
+    }
+    {
+        ProfScope ps(ctx, "eddsa_sign_points", (double)count * 256.0);
+        hipLaunchKernelGGL(k_eddsa_sign_points, grid, block, 0, ctx->stream, table, k, d_keys, st.rho.p, d_msgs, count, d_points);
+        ZK_HIP(hipGetLastError());
+    }
+    {
+        ProfScope ps(ctx, "eddsa_sign_response", (double)count * (288.0 + (d_bits ? 64.0 : 0.0)));
+        hipLaunchKernelGGL(k_eddsa_sign_response, grid, block, 0, ctx->stream, st.par.p, d_keys, st.rho.p, d_points, count, d_s, d_bits, bits_stride_words);
+        ZK_HIP(hipGetLastError());
+    }
+    ZK_HIP(hipStreamSynchronize(ctx->stream));
+    ctx->resolve_profile();
+}
+
 }  // namespace zk
 
 using namespace zk;
 
 extern "C" {
+
+int zk_eddsa_sign_batch(zk_ctx* ctx, const void* d_keys, const void* d_nonce_keys, const void* d_msgs, size_t count, void* d_points_msg_out,
+                        void* d_s_out, void* d_bits_out, size_t bits_stride_bytes) {
+    if (!ctx) return ZK_ERR_ARG;
+    return guarded(ctx, [&] {
+        ZK_REQUIRE(!d_bits_out || (bits_stride_bytes >= 8 * EDDSA_BITS_WORDS && bits_stride_bytes % 8 == 0), ZK_ERR_ARG,
+                   "eddsa: bits_stride_bytes must be a multiple of 8 and at least 64, got " + std::to_string(bits_stride_bytes));
+        if (count == 0) return;
+        ZK_REQUIRE(d_keys && d_nonce_keys && d_msgs && d_points_msg_out && d_s_out, ZK_ERR_ARG, "eddsa: null device pointer");
+        ZK_REQUIRE(((uintptr_t)d_keys | (uintptr_t)d_nonce_keys | (uintptr_t)d_msgs | (uintptr_t)d_points_msg_out | (uintptr_t)d_s_out |
+                    (uintptr_t)d_bits_out) % 8 == 0,
+                   ZK_ERR_ARG, "eddsa: the device pointers must be 8-byte aligned");
+        eddsa_sign_batch(ctx, (const uint64_t*)d_keys, (const uint64_t*)d_nonce_keys, (const uint64_t*)d_msgs, count, (uint64_t*)d_points_msg_out,
+                         (uint64_t*)d_s_out, (uint64_t*)d_bits_out, bits_stride_bytes / 8);
+    });
+}
 
 int zk_eddsa_verify_batch(zk_ctx* ctx, const void* d_points_msg, const void* d_s, size_t count, void* d_status, void* d_bits_out,
                           size_t bits_stride_bytes) {

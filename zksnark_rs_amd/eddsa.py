@@ -5,6 +5,7 @@
     public_key(k), sign(k, nonce_key, msg)      host code, no context (zk_eddsa_public_key / _sign); signing is deterministic
     verify(a, msg, r8, s)                       -> a status, VALID .. MISMATCH (zk_eddsa_verify); a malformed signature is a verdict
     Context.eddsa_verify_batch(...)             one verdict per lane on the GPU, and the bit rows of the circuit (zk_eddsa_verify_batch)
+    Context.eddsa_sign_batch(...)               one signature per lane on the GPU: the inputs of verify_batch and its bit rows (zk_eddsa_sign_batch)
     circuit.Builder.eddsa_verify(...)           the statement as sub-circuits (zk_builder_eddsa_verify)
 """
 import ctypes as C
